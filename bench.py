@@ -24,9 +24,16 @@ update; nothing is skipped or cached.  step_time_p50/p90 come from per-step
 device timestamps (s_memrealtime at every step start) on the persistent
 engines.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: either under python -m torch.distributed.run --nproc-per-node N ...,
      or plain: bench.py then starts the N rank processes itself)
+
+A plain run sets up, warms up, times exactly K steps and prints the result line:
+that is all the headline figure needs.  `--dump-outputs DIR` also writes what
+the timed steps left behind (`dump_outputs`).  `--full` is where measurements
+beyond the headline belong (other precisions, baselines, per-kernel figures);
+this benchmark has none of its own -- they live in scripts/ -- so today it
+runs the same steps as a plain run.
 
 Rank 0 prints ONE JSON line.
 """
@@ -106,6 +113,7 @@ if __name__ == "__main__" and "WORLD_SIZE" not in os.environ:
     if _n > 1:
         sys.exit(self_launch(sys.argv[1:], _n))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 REPO = os.path.dirname(os.path.abspath(__file__))
@@ -119,6 +127,19 @@ from distributed_tensorflow_example_amd.models.mlp import (  # noqa: E402
 from distributed_tensorflow_example_amd.parallel import world as world_mod  # noqa: E402
 
 METRIC = "samples/sec (whole node) MNIST MLP sync-SGD at 1/2/4/8 MI355X; step-time p50"
+
+
+def dump_outputs(out_dir: str, trainer) -> None:
+    """What a caller of the timed path holds after its last step, as float32
+    `<name>.npy` files (320 KB in all): `params` -- the flat fp32 master weights
+    (W1, W2, b1, b2: models/mlp.py) the last SGD update left -- and
+    `last_step_metrics` -- that step's (loss, batch accuracy).  Data, initial
+    weights and batch order are seeded, so two builds run with the same
+    arguments can be compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = trainer.global_step
+    np.save(os.path.join(out_dir, "params.npy"), trainer.get_params().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "last_step_metrics.npy"), trainer.read_metrics(g - 1, g)[0].astype(np.float32))
 
 
 def main(argv=None):
@@ -157,6 +178,12 @@ def main(argv=None):
                          "IPC one-shot in a separate reduce+apply kernel (ipc-apply), or RCCL")
     ap.add_argument("--rccl-timeout", type=float, default=120.0,
                     help="N>1: bound on RCCL communicator creation (s); a failure is recorded in the fallbacks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (final params, last step's loss / "
+                         "accuracy) as DIR/<name>.npy; same arguments -> same inputs, so builds compare file for file")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none in this benchmark today: "
+                         "baselines, other models and per-kernel figures are separate programs under scripts/)")
     a = ap.parse_args(argv)
 
     world_size_env = int(os.environ.get("WORLD_SIZE", "1"))
@@ -407,6 +434,8 @@ def main(argv=None):
         print(json.dumps({"metric": METRIC, "error": "non-finite final loss / accuracy; result discarded",
                           "final_loss": float(m[0])}), file=sys.stderr, flush=True)
         raise SystemExit(3)
+    if a.dump_outputs and w.rank == 0:   # replicas are bit-identical (checked above): rank 0's copy is the result
+        dump_outputs(a.dump_outputs, trainer)
     n = w.world_size
     samples_per_s = n * a.batch * a.steps / elapsed_max
     if w.rank == 0:

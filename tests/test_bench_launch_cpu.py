@@ -69,6 +69,32 @@ def test_self_launch_terminates_hung_rank_after_failure(tmp_path):
     assert dt < 60, dt
 
 
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    """`--dump-outputs DIR`: the final flat params and the last step's (loss,
+    accuracy) as float32 DIR/<name>.npy, read through the trainer's own accessors."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    class Trainer:
+        global_step = 7
+
+        def get_params(self):
+            return torch.arange(5, dtype=torch.float32)
+
+        def read_metrics(self, first, last):
+            assert (first, last) == (6, 7)
+            return np.array([[0.25, 0.5]], dtype=np.float32)
+
+    out = tmp_path / "a" / "b"                # created if missing
+    bench.dump_outputs(str(out), Trainer())
+    assert sorted(p.name for p in out.iterdir()) == ["last_step_metrics.npy", "params.npy"]
+    p, m = np.load(out / "params.npy"), np.load(out / "last_step_metrics.npy")
+    assert p.dtype == np.float32 and p.tolist() == [0, 1, 2, 3, 4]
+    assert m.dtype == np.float32 and m.tolist() == [0.25, 0.5]
+
+
 def _ensure_comm_worker(rank, world, port, fault, q):
     import datetime
 

@@ -306,6 +306,40 @@ def test_bench_self_launch_without_torchrun(native, n):
     assert res["value"] > 0
 
 
+def test_bench_dump_outputs_repeatable(native, tmp_path):
+    """`bench.py --gpus 1 --steps K --dump-outputs DIR`: exactly K timed steps,
+    `ms_per_step` on the line, and the final params / last step's metrics written
+    as float32 .npy -- bit-identical between two runs with the same arguments
+    (seeded data, weights and batch order; one GPU has no exchange to reorder
+    sums), so two builds can be compared output for output."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(PYTHONPATH=repo, OMP_NUM_THREADS="2")
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+               "--train-examples", "2000", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=repo)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]
+        res = json.loads(lines[0])
+        assert res["steps"] == 20 and res["global_steps_timed"] == 20 and res["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["last_step_metrics.npy", "params.npy"]
+        p, m = np.load(d / "params.npy"), np.load(d / "last_step_metrics.npy")
+        assert p.dtype == np.float32 and p.shape == (mlp.NPARAM,) and np.isfinite(p).all()
+        assert m.dtype == np.float32 and m.shape == (2,)
+        assert round(float(m[0]), 5) == res["final_loss"] and round(float(m[1]), 4) == res["final_batch_acc"]
+        assert not np.array_equal(p, mlp.init_params(1).numpy())      # the steps trained
+        dumps.append((p, m))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
 def test_bench_rccl_init_failure_still_measures(native):
     """RCCL that cannot come up (injected init fault) costs only the RCCL
     strategy: it is tried first here (DTF_BENCH_CHAIN), recorded under
