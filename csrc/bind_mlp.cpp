@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "comm/ipc_coll_host.h"
+#include "kernels/mlp_api.h"
 
 #include <algorithm>
 #include <atomic>
@@ -14,69 +15,6 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
-
-extern "C" {
-int dtfk_mlp_ksplit();
-hipError_t dtfk_mlp_l1_fwd(const void* x, int x_kind, int B, const void* W1T, float* z2p,
-                           long long* ts, hipStream_t stream);
-hipError_t dtfk_mlp_head_bwd(const float* a2, const void* labels, int B, const void* W2T,
-                             const void* W2N, const float* params, void* dz2T, int BP, float* partials,
-                             float inv_batch, int act, int naive_loss, long long* gstep, long long* ts,
-                             hipStream_t stream);
-hipError_t dtfk_mlp_wgrad(const void* x, int x_kind, const void* dz2T, int BP, int B,
-                          const float* partials, float* params, void* W1T, void* W2T, void* W2N,
-                          void* grads, int grad_kind, const float* lr, float* metrics,
-                          long long* gstep, int ring, long long* ts, void* const* ipc_table, int ipc_W,
-                          int ipc_rank, int ipc_parity, long long ipc_slot_bytes, int* ipc_err,
-                          long long ipc_timeout, hipStream_t stream);
-hipError_t dtfk_mlp_apply_flat(float* params, const void* grads, int grad_kind, const float* lr,
-                               float scale, void* W1T, void* W2T, void* W2N, hipStream_t stream);
-int dtfk_mlp_ipc_flag_bytes();
-int dtfk_mlpg_p1_floats();
-hipError_t dtfk_mlpg_fwd(const void* x, const void* labels, int B, int BP, const void* W1F, const float* params,
-                         float* a2g, float* P1, void* dz2F, int act, int naive, float gscale, hipStream_t s);
-hipError_t dtfk_mlpg_wgrad(const void* x, int B, const void* dz2F, float* P2, int nchunk, hipStream_t s);
-int dtfk_mlpg_wchunk(int B);
-int dtfk_mlpg_p2_floats();
-hipError_t dtfk_mlpg_apply(float* params, const float* P1, int n1, const float* P2, int n2, const float* gin,
-                           float* gout, const float* lr, float scale, void* W1S, float* metrics, int ring,
-                           long long* gstep, int B, int mode, hipStream_t s);
-hipError_t dtfk_mlp_ipc_reduce_apply(float* params, void* const* peer_table, int W, int rank, int parity,
-                                     long long slot_bytes, const long long* gstep, const float* lr, float scale,
-                                     void* W1T, void* W2T, void* W2N, int* err, long long timeout_ticks,
-                                     hipStream_t stream);
-long long dtfk_mlpf_stage_rec();
-void dtfk_mlpf_set_fault(int rank, long long step);
-void dtfk_mlpf_set_res_ts(long long* p);
-long long dtfk_mlpf_xbuf_bytes();
-long long dtfk_mlpf_ipc_bytes();
-int dtfk_mlpf_max_batch();
-hipError_t dtfk_mlp_persist_f32(const void* stage, long long rec_h, int B, int nsteps, float* params, const float* lr,
-                                float* metrics, int ring, int act, int naive, long long* gstep, unsigned long long* seq,
-                                void* xbuf, int* err, long long timeout, long long* step_ts, int ts_ring,
-                                const void* host_next, int next_steps, void* stage_next, void* const* peer_base, int W,
-                                int rank, int gbf16, long long* phase_ts, int spread, int xmode, int split,
-                                hipStream_t stream);
-hipError_t dtfk_mlp_persist_f32_resident(void* stage, int B, float* W1, float* W2, float* b1, float* b2, const float* lr,
-                                         float* metrics, int ring, int act, int naive, long long* gstep,
-                                         unsigned long long* seq, void* xbuf, int* err, long long timeout,
-                                         const long long* door, const void* host_recs, long long rec_h,
-                                         const float* host_lr, float* host_out, long long* host_done,
-                                         long long* host_state, long long launch_id, long long run0, long long idle,
-                                         void* gvar, int gvar_kind, unsigned* dctr, hipStream_t stream);
-long long dtfk_graph_mlp_part_floats(int B, int H);
-hipError_t dtfk_graph_feed_ingest(const void* host, void* dev, long long bytes, hipStream_t stream);
-hipError_t dtfk_graph_mlp_step(const float* x, const uint8_t* xu, const float* ylab, float* W1, float* b1, float* W2,
-                               float* b2,
-                               float* a2buf, float* dz2buf, float* part, float* gW1, float* gb1, float* gW2,
-                               float* gb2, float* metrics, float* host_metrics, void* gstep, int gstep_kind,
-                               const float* lr_ptr, int B, int K, int H, int C, int act, int naive, int sgd,
-                               hipStream_t stream);
-hipError_t dtfk_mlp_fwd_head(const void* x, int x_kind, int B, const void* W1T, float* z2p, const void* labels,
-                             const void* W2T, const void* W2N, const float* params, void* dz2T, int BP,
-                             float* partials, float inv_batch, int act, int naive_loss, int* counters,
-                             long long* gstep, hipStream_t stream);
-}
 
 namespace dtf {
 
@@ -101,15 +39,6 @@ static long long* ts_ptr(const c10::optional<at::Tensor>& ts, int64_t need_numel
   if (!ts.has_value()) return nullptr;
   need(*ts, at::kLong, need_numel, "ts");
   return reinterpret_cast<long long*>(ts->data_ptr<int64_t>());
-}
-
-// optional per-step s_memrealtime ring (int64)
-static long long* step_ts_ptr(const c10::optional<at::Tensor>& t, int* ring) {
-  *ring = 1;
-  if (!t.has_value()) return nullptr;
-  need(*t, at::kLong, 2, "step_ts");
-  *ring = (int)t->numel();
-  return reinterpret_cast<long long*>(t->data_ptr<int64_t>());
 }
 
 // device-visible address of `nbytes` of pinned host memory at `off`
@@ -370,83 +299,29 @@ void memcpy_h2d_async(at::Tensor dst, int64_t dst_offset, at::Tensor src, int64_
             "hipMemcpyAsync");
 }
 
-// The fp32 persistent engine (csrc/kernels/mlp_persist_f32.hip; mfma_split: the big
-// GEMMs as exact 3-way bf16 splits, else f32-input MFMA): `nsteps` SGD steps of
-// the chunk staged in `stage` (records of mlpf_stage_rec() bytes) and, in the same
-// launch, `next_steps` host records from byte `host_off` of the pinned epoch into
-// `stage_next`.  nsteps = 0: copy only.  xbuf: exchange buffer (zeroed once).
-void mlp_persist_f32(at::Tensor stage, int64_t rec_h, int B, int nsteps, at::Tensor params, at::Tensor lr,
-                     at::Tensor metrics, at::Tensor gstep, at::Tensor seq, at::Tensor xbuf, at::Tensor err,
-                     double timeout_s, int act, int naive, c10::optional<at::Tensor> host, int64_t host_off,
-                     int next_steps, c10::optional<at::Tensor> stage_next, c10::optional<at::Tensor> step_ts,
-                     int64_t ipc_table, int ipc_W, int ipc_rank, bool grad_bf16,
-                     c10::optional<at::Tensor> phase_ts, bool spread, bool two_shot, bool mfma_split) {
-  if (ipc_W > 1 && (ipc_table == 0 || ipc_rank < 0 || ipc_rank >= ipc_W || ipc_W > 64))
-    throw std::runtime_error("mlp_persist_f32: N-GPU exchange needs the IPC peer table");
-  if (B <= 0 || B > dtfk_mlpf_max_batch()) throw std::runtime_error("mlp_persist_f32: B out of range");
-  if (rec_h < (int64_t)B * 785 || rec_h % 16 != 0) throw std::runtime_error("mlp_persist_f32: bad host record size");
-  if (nsteps < 0 || next_steps < 0) throw std::runtime_error("mlp_persist_f32: negative step count");
-  const int64_t rec_s = dtfk_mlpf_stage_rec();
-  need(stage, at::kByte, (int64_t)std::max(nsteps, 1) * rec_s, "stage");
-  need(params, at::kFloat, kNParam, "params");
-  need(lr, at::kFloat, 1, "lr");
-  need(metrics, at::kFloat, 2, "metrics");
-  need(gstep, at::kLong, 1, "gstep");
-  need(seq, at::kLong, 1, "seq");
-  need(xbuf, at::kByte, dtfk_mlpf_xbuf_bytes(), "xbuf");
-  need(err, at::kInt, 1, "err");
-  if (((uintptr_t)stage.data_ptr() | (uintptr_t)xbuf.data_ptr()) % 16 != 0)
-    throw std::runtime_error("mlp_persist_f32: stage / xbuf must be 16-byte aligned");
-  const void* hn = nullptr;
-  void* sn = nullptr;
-  if (next_steps > 0) {
-    if (!stage_next.has_value()) throw std::runtime_error("mlp_persist_f32: next chunk needs stage_next");
-    need(*stage_next, at::kByte, (int64_t)next_steps * rec_s, "stage_next");
-    if ((uintptr_t)stage_next->data_ptr() % 16 != 0) throw std::runtime_error("stage_next must be 16-byte aligned");
-    if (stage_next->data_ptr() == stage.data_ptr() && nsteps > 0)
-      throw std::runtime_error("mlp_persist_f32: stage_next must not alias the running stage");
-    hn = pinned_device_ptr(host, host_off, (int64_t)next_steps * rec_h);
-    sn = stage_next->data_ptr();
-  }
-  int ts_ring = 1;
-  long long* sts = step_ts_ptr(step_ts, &ts_ring);
-  const long long ticks = (long long)(timeout_s * 1e8);   // s_memrealtime: 100 MHz
-  const hipError_t e =
-      dtfk_mlp_persist_f32(stage.data_ptr(), rec_h, B, nsteps, params.data_ptr<float>(), lr.data_ptr<float>(),
-                             metrics.data_ptr<float>(), (int)(metrics.numel() / 2), act, naive,
-                             reinterpret_cast<long long*>(gstep.data_ptr<int64_t>()),
-                             reinterpret_cast<unsigned long long*>(seq.data_ptr<int64_t>()), xbuf.data_ptr(),
-                             err.data_ptr<int>(), ticks, sts, ts_ring, hn, next_steps, sn,
-                             reinterpret_cast<void* const*>(ipc_table), ipc_W > 1 ? ipc_W : 1,
-                             ipc_W > 1 ? ipc_rank : 0, grad_bf16 ? 1 : 0, ts_ptr(phase_ts, 65 * 64 * 16),
-                             spread ? 1 : 0, two_shot ? 1 : 0, mfma_split ? 1 : 0, cur_stream());
-  hip_check(e,
-            "mlp_persist_f32");
-}
-
-// A prepared launcher for the fp32 persistent engine: every tensor checked and
-// every pointer resolved once, so a launch from Python is a call with 6 ints
-// (the generic binding's ~27 keyword arguments and per-call checks cost ~10 us
-// of host time on a 20-step run: scripts/probes/launch_overhead.py).
+// A prepared launcher for the fp32 persistent engine (csrc/kernels/mlp_persist_f32.hip;
+// mfma_split: the big GEMMs as exact 3-way bf16 splits, else f32-input MFMA):
+// every tensor checked and every pointer resolved once into the launch struct,
+// so a launch from Python is a call with 5 ints that patches the per-launch
+// fields (per-call tensor arguments and checks cost ~10 us of host time on a
+// 20-step run: scripts/probes/launch_overhead.py).
 struct PersistF32Plan {
-  at::Tensor stage0, stage1, params, lr, metrics, gstep, seq, xbuf, err, step_ts, host;
+  at::Tensor stage0, stage1, params, lr, metrics, gstep, seq, xbuf, err, step_ts, host, phase_ts;
   void* st[2];
   const char* host_dev = nullptr;
-  int64_t host_bytes = 0, rec_h = 0, rec_s = 0;
-  int B, act, naive, ring, ts_ring = 1, W, rank, gbf16, spread, two_shot, split;
-  long long ticks;
-  int64_t ipc_table;
+  int64_t host_bytes = 0, rec_s = 0;
+  dtfk::mlpf::Launch p{};
 
-  PersistF32Plan(at::Tensor s0, at::Tensor s1, int64_t rec_h_, int B_, at::Tensor params_, at::Tensor lr_,
+  PersistF32Plan(at::Tensor s0, at::Tensor s1, int64_t rec_h, int B, at::Tensor params_, at::Tensor lr_,
                  at::Tensor metrics_, at::Tensor gstep_, at::Tensor seq_, at::Tensor xbuf_, at::Tensor err_,
-                 double timeout_s, int act_, int naive_, at::Tensor host_, at::Tensor step_ts_, int64_t ipc_table_,
-                 int ipc_W, int ipc_rank, bool grad_bf16, bool spread_, bool two_shot_, bool mfma_split)
+                 double timeout_s, int act, int naive, at::Tensor host_, at::Tensor step_ts_, int64_t ipc_table,
+                 int ipc_W, int ipc_rank, bool grad_bf16, bool spread, bool two_shot, bool mfma_split)
       : stage0(s0), stage1(s1), params(params_), lr(lr_), metrics(metrics_), gstep(gstep_), seq(seq_), xbuf(xbuf_),
         err(err_), step_ts(step_ts_), host(host_) {
-    if (ipc_W > 1 && (ipc_table_ == 0 || ipc_rank < 0 || ipc_rank >= ipc_W || ipc_W > 64))
+    if (ipc_W > 1 && (ipc_table == 0 || ipc_rank < 0 || ipc_rank >= ipc_W || ipc_W > 64))
       throw std::runtime_error("PersistF32Plan: N-GPU exchange needs the IPC peer table");
-    if (B_ <= 0 || B_ > dtfk_mlpf_max_batch()) throw std::runtime_error("PersistF32Plan: B out of range");
-    if (rec_h_ < (int64_t)B_ * 785 || rec_h_ % 16 != 0) throw std::runtime_error("PersistF32Plan: bad record size");
+    if (B <= 0 || B > dtfk_mlpf_max_batch()) throw std::runtime_error("PersistF32Plan: B out of range");
+    if (rec_h < (int64_t)B * 785 || rec_h % 16 != 0) throw std::runtime_error("PersistF32Plan: bad record size");
     rec_s = dtfk_mlpf_stage_rec();
     need(stage0, at::kByte, rec_s, "stage0");
     need(stage1, at::kByte, rec_s, "stage1");
@@ -464,47 +339,57 @@ struct PersistF32Plan {
       throw std::runtime_error("PersistF32Plan: stage / xbuf must be 16-byte aligned");
     host_bytes = host.numel() * host.element_size();
     host_dev = static_cast<const char*>(pinned_device_ptr(host, 0, host_bytes));
-    rec_h = rec_h_;
-    B = B_;
-    act = act_;
-    naive = naive_;
-    ring = (int)(metrics.numel() / 2);
-    ts_ring = (int)step_ts.numel();
-    ticks = (long long)(timeout_s * 1e8);
-    ipc_table = ipc_table_;
-    W = ipc_W > 1 ? ipc_W : 1;
-    rank = ipc_W > 1 ? ipc_rank : 0;
-    gbf16 = grad_bf16 ? 1 : 0;
-    spread = spread_ ? 1 : 0;
-    two_shot = two_shot_ ? 1 : 0;
-    split = mfma_split ? 1 : 0;
+    p.rec_h = rec_h;
+    p.B = B;
+    p.params = params.data_ptr<float>();
+    p.lr = lr.data_ptr<float>();
+    p.metrics = metrics.data_ptr<float>();
+    p.ring = (int)(metrics.numel() / 2);
+    p.act = act;
+    p.naive = naive;
+    p.gstep = reinterpret_cast<long long*>(gstep.data_ptr<int64_t>());
+    p.seq = reinterpret_cast<unsigned long long*>(seq.data_ptr<int64_t>());
+    p.xbuf = xbuf.data_ptr();
+    p.err = err.data_ptr<int>();
+    p.timeout = (long long)(timeout_s * 1e8);   // s_memrealtime: 100 MHz
+    p.step_ts = reinterpret_cast<long long*>(step_ts.data_ptr<int64_t>());
+    p.ts_ring = (int)step_ts.numel();
+    p.peer_base = reinterpret_cast<void* const*>(ipc_table);
+    p.W = ipc_W > 1 ? ipc_W : 1;
+    p.rank = ipc_W > 1 ? ipc_rank : 0;
+    p.gbf16 = grad_bf16 ? 1 : 0;
+    p.spread = spread ? 1 : 0;
+    p.xmode = two_shot ? 1 : 0;
+    p.split = mfma_split ? 1 : 0;
   }
 
-  // nsteps steps from stage `par` at step offset `off`; next_steps host records from
-  // byte host_off into stage par ^ 1 (same contract as mlp_persist_f32 above)
+  // profiling: phase stamps [65][64][16] on (the instrumented build, one GPU) / off (None)
+  void set_phase_ts(c10::optional<at::Tensor> ts) {
+    p.phase_ts = ts_ptr(ts, 65 * 64 * 16);
+    phase_ts = ts.has_value() ? *ts : at::Tensor();
+  }
+
+  // nsteps steps from stage `par` at step offset `off` (records of mlpf_stage_rec()
+  // bytes) and, in the same launch, next_steps host records from byte host_off of
+  // the pinned epoch into stage par ^ 1.  nsteps = 0: copy only.
   void launch(int par, int64_t off, int nsteps, int64_t host_off, int next_steps) {
     if ((par & ~1) != 0 || nsteps < 0 || next_steps < 0 || off < 0) throw std::runtime_error("PersistF32Plan: args");
     const at::Tensor& cur = par ? stage1 : stage0;
     const at::Tensor& nxt = par ? stage0 : stage1;
     if ((off + std::max(nsteps, 1)) * rec_s > cur.numel()) throw std::runtime_error("PersistF32Plan: stage overrun");
-    const void* hn = nullptr;
-    void* sn = nullptr;
+    p.host_next = nullptr;
+    p.stage_next = nullptr;
     if (next_steps > 0) {
       if ((int64_t)next_steps * rec_s > nxt.numel()) throw std::runtime_error("PersistF32Plan: next stage too small");
-      if (host_off < 0 || host_off % 16 != 0 || host_off + (int64_t)next_steps * rec_h > host_bytes)
+      if (host_off < 0 || host_off % 16 != 0 || host_off + (int64_t)next_steps * p.rec_h > host_bytes)
         throw std::runtime_error("PersistF32Plan: host range out of bounds");
-      hn = host_dev + host_off;
-      sn = st[par ^ 1];
+      p.host_next = host_dev + host_off;
+      p.stage_next = st[par ^ 1];
     }
-    hip_check(dtfk_mlp_persist_f32(static_cast<const char*>(st[par]) + off * rec_s, rec_h, B, nsteps,
-                                   params.data_ptr<float>(), lr.data_ptr<float>(), metrics.data_ptr<float>(), ring,
-                                   act, naive, reinterpret_cast<long long*>(gstep.data_ptr<int64_t>()),
-                                   reinterpret_cast<unsigned long long*>(seq.data_ptr<int64_t>()), xbuf.data_ptr(),
-                                   err.data_ptr<int>(), ticks,
-                                   reinterpret_cast<long long*>(step_ts.data_ptr<int64_t>()), ts_ring, hn,
-                                   next_steps, sn, reinterpret_cast<void* const*>(ipc_table), W, rank, gbf16,
-                                   nullptr, spread, two_shot, split, cur_stream()),
-              "PersistF32Plan.launch");
+    p.stage = static_cast<const char*>(st[par]) + off * rec_s;
+    p.nsteps = nsteps;
+    p.next_steps = next_steps;
+    hip_check(dtfk_mlp_persist_f32_launch(&p, cur_stream()), "PersistF32Plan.launch");
   }
 };
 
@@ -1088,19 +973,40 @@ class ResidentMLPPlan {
     hip_check(hipMemsetAsync(dctr_.data_ptr(), 0, dctr_.numel() * sizeof(int), st_), "ResidentMLPPlan: counters");
     if (__atomic_load_n(door_, __ATOMIC_ACQUIRE) < 0) __atomic_store_n(door_, runs_, __ATOMIC_RELEASE);   // after stop()
     ++launch_id_;
-    dtfk_mlpf_set_res_ts(res_ts_.defined() ? reinterpret_cast<long long*>(res_ts_.data_ptr<int64_t>()) : nullptr);
-    hip_check(dtfk_mlp_persist_f32_resident(
-                  stage_.data_ptr(), B_, W1_.data_ptr<float>(), W2_.data_ptr<float>(), b1_.data_ptr<float>(),
-                  b2_.data_ptr<float>(), lrdev_.data_ptr<float>(), metrics_.data_ptr<float>(), kRing, act_,
-                  naive_ ? 1 : 0, reinterpret_cast<long long*>(kgstep_.data_ptr<int64_t>()),
-                  reinterpret_cast<unsigned long long*>(seq_.data_ptr<int64_t>()), xbuf_.data_ptr(),
-                  err_.data_ptr<int>(), timeout_, reinterpret_cast<const long long*>(dmail_),
-                  dmail_ + 512, rec_h_, reinterpret_cast<const float*>(dmail_ + 256),
-                  reinterpret_cast<float*>(dmail_ + 192), reinterpret_cast<long long*>(dmail_ + 64),
-                  reinterpret_cast<long long*>(dmail_ + 128), launch_id_, runs_, idle_,
-                  gkind_ ? gstep_.data_ptr() : nullptr, gkind_, reinterpret_cast<unsigned*>(dctr_.data_ptr<int>()),
-                  st_),
-              "ResidentMLPPlan: launch");
+    dtfk::mlpf::Launch p{};
+    p.stage = stage_.data_ptr();
+    p.rec_h = rec_h_;
+    p.B = B_;
+    p.params = W1_.data_ptr<float>();
+    p.W2 = W2_.data_ptr<float>();
+    p.b1 = b1_.data_ptr<float>();
+    p.b2 = b2_.data_ptr<float>();
+    p.lr = lrdev_.data_ptr<float>();
+    p.metrics = metrics_.data_ptr<float>();
+    p.ring = kRing;
+    p.act = act_;
+    p.naive = naive_ ? 1 : 0;
+    p.gstep = reinterpret_cast<long long*>(kgstep_.data_ptr<int64_t>());
+    p.seq = reinterpret_cast<unsigned long long*>(seq_.data_ptr<int64_t>());
+    p.xbuf = xbuf_.data_ptr();
+    p.err = err_.data_ptr<int>();
+    p.timeout = timeout_;
+    p.W = 1;
+    p.split = 1;
+    p.door = reinterpret_cast<const long long*>(dmail_);
+    p.host_recs = dmail_ + 512;
+    p.host_lr = reinterpret_cast<const float*>(dmail_ + 256);
+    p.host_out = reinterpret_cast<float*>(dmail_ + 192);
+    p.host_done = reinterpret_cast<long long*>(dmail_ + 64);
+    p.host_state = reinterpret_cast<long long*>(dmail_ + 128);
+    p.launch_id = launch_id_;
+    p.run0 = runs_;
+    p.idle = idle_;
+    p.gvar = gkind_ ? gstep_.data_ptr() : nullptr;
+    p.gvar_kind = gkind_;
+    p.dctr = reinterpret_cast<unsigned*>(dctr_.data_ptr<int>());
+    p.res_ts = res_ts_.defined() ? reinterpret_cast<long long*>(res_ts_.data_ptr<int64_t>()) : nullptr;
+    hip_check(dtfk_mlp_persist_f32_launch(&p, st_), "ResidentMLPPlan: launch");
     alive_ = true;
   }
 
@@ -1157,17 +1063,11 @@ void init_mlp(py::module& m) {
   m.def("graph_mlp_step", &graph_mlp_step, py::arg("x"), py::arg("ylab"), py::arg("W1"), py::arg("b1"),
         py::arg("W2"), py::arg("b2"), py::arg("a2buf"), py::arg("dz2buf"), py::arg("grads"), py::arg("metrics"),
         py::arg("gstep"), py::arg("lr"), py::arg("act"), py::arg("naive"), py::arg("sgd"));
-  m.def("mlp_persist_f32", &mlp_persist_f32, py::arg("stage"), py::arg("rec_h"), py::arg("B"), py::arg("nsteps"),
-        py::arg("params"), py::arg("lr"), py::arg("metrics"), py::arg("gstep"), py::arg("seq"), py::arg("xbuf"),
-        py::arg("err"), py::arg("timeout_s"), py::arg("act"), py::arg("naive"), py::arg("host") = py::none(),
-        py::arg("host_offset") = 0, py::arg("next_steps") = 0, py::arg("stage_next") = py::none(),
-        py::arg("step_ts") = py::none(), py::arg("ipc_table") = 0, py::arg("ipc_W") = 1, py::arg("ipc_rank") = 0,
-        py::arg("grad_bf16") = true, py::arg("phase_ts") = py::none(), py::arg("spread") = false,
-        py::arg("two_shot") = false, py::arg("mfma_split") = false);
   py::class_<PersistF32Plan>(m, "PersistF32Plan")
       .def(py::init<at::Tensor, at::Tensor, int64_t, int, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, double, int, int, at::Tensor, at::Tensor, int64_t, int, int,
                     bool, bool, bool, bool>())
+      .def("set_phase_ts", &PersistF32Plan::set_phase_ts, py::arg("phase_ts"))
       .def("launch", &PersistF32Plan::launch);
   m.def("mlpf_stage_rec", &dtfk_mlpf_stage_rec);
   m.def("mlpf_set_fault", &dtfk_mlpf_set_fault, py::arg("rank"), py::arg("step"));

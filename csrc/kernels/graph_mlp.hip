@@ -31,6 +31,7 @@
 // Shapes: any B <= 256 with B*HP <= 16384 (HP = H + 1 rounded up to 16),
 // K >= 1, H <= 128, C <= 16.
 #include "common.h"
+#include "mlp_api.h"
 
 #include <algorithm>
 

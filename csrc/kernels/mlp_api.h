@@ -1,0 +1,110 @@
+// The host entry points of the MLP kernel files (mlp_step.hip, mlp_gemm.hip,
+// mlp_persist_f32.hip, graph_mlp.hip), declared once: csrc/bind_mlp.cpp calls
+// through these declarations and every defining file includes them, so a
+// definition that disagrees with its declaration does not compile.  Host-only:
+// no device code here.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+namespace dtfk {
+namespace mlpf {
+
+// One launch of the fp32 persistent engine (mlp_persist_f32.hip).  Value-
+// initialise it (`Launch p{}`) and set what the mode needs; everything else
+// stays null / zero.
+struct Launch {
+  const void* stage;        // flat: this chunk, nsteps records; resident: 2 device record slots
+  long long rec_h;          // host record bytes (B * 785 rounded up to 16)
+  int B, nsteps;            // nsteps: flat only (0: copy only); a resident launch runs until its doorbell stops it
+  float* params;            // W1, the front of the flat fp32 master
+  float* W2;                // null: the flat master's own (params + OFF_W2 / OFF_B1 / OFF_B2);
+  float* b1;                //   resident: the graph's variables
+  float* b2;
+  const float* lr;
+  float* metrics;
+  int ring;                 // metrics ring: [ring][2]
+  int act, naive;
+  long long* gstep;
+  unsigned long long* seq;  // exchange sequence number (monotonic across launches)
+  void* xbuf;               // granule exchange buffer (dtfk_mlpf_xbuf_bytes(), zeroed once)
+  int* err;
+  long long timeout;        // s_memrealtime ticks (100 MHz)
+  long long* step_ts;       // optional per-step stamp ring of ts_ring entries
+  int ts_ring;
+  const void* host_next;    // next chunk: next_steps host records (device-visible pinned memory) -> stage_next
+  int next_steps;
+  void* stage_next;
+  void* const* peer_base;   // N GPUs: IPC-mapped exchange buffers of every rank
+  int W, rank;              // 1 <= W <= 8 (1: one GPU), 0 <= rank < W
+  int gbf16, spread, xmode; // dW1 payload in bf16; spread placement; 1: two-shot exchange
+  int split;                // 1: the big GEMMs as exact 3-way bf16 splits, 0: f32-input MFMA
+  long long* phase_ts;      // profiling: [65][64][16] phase stamps -> the instrumented build (one GPU)
+  // resident mode (door != nullptr): the Session engine's pinned mailbox
+  const long long* door;
+  const void* host_recs;
+  const float* host_lr;
+  float* host_out;
+  long long* host_done;
+  long long* host_state;
+  long long launch_id, run0, idle;
+  void* gvar;               // the graph's global_step variable (kind 0 none, 1 f32, 2 i64, 3 i32, 4 f64)
+  int gvar_kind;
+  unsigned* dctr;
+  long long* res_ts;        // profiling: [64][8] per-run stamps -> the instrumented resident build
+};
+
+}  // namespace mlpf
+}  // namespace dtfk
+
+extern "C" {
+// ---- mlp_step.hip
+int dtfk_mlp_ksplit();
+hipError_t dtfk_mlp_l1_fwd(const void* x, int x_kind, int B, const void* W1T, float* z2p, long long* ts,
+                           hipStream_t stream);
+hipError_t dtfk_mlp_fwd_head(const void* x, int x_kind, int B, const void* W1T, float* z2p, const void* labels,
+                             const void* W2T, const void* W2N, const float* params, void* dz2T, int BP,
+                             float* partials, float inv_batch, int act, int naive_loss, int* counters,
+                             long long* gstep, hipStream_t stream);
+hipError_t dtfk_mlp_head_bwd(const float* z2p, const void* labels, int B, const void* W2T, const void* W2N,
+                             const float* params, void* dz2T, int BP, float* partials, float inv_batch, int act,
+                             int naive_loss, long long* gstep, long long* ts, hipStream_t stream);
+hipError_t dtfk_mlp_wgrad(const void* x, int x_kind, const void* dz2T, int BP, int B, const float* partials,
+                          float* params, void* W1T, void* W2T, void* W2N, void* grads, int grad_kind, const float* lr,
+                          float* metrics, long long* gstep, int ring, long long* ts, void* const* ipc_table, int ipc_W,
+                          int ipc_rank, int ipc_parity, long long ipc_slot_bytes, int* ipc_err, long long ipc_timeout,
+                          hipStream_t stream);
+hipError_t dtfk_mlp_apply_flat(float* params, const void* grads, int grad_kind, const float* lr, float scale,
+                               void* W1T, void* W2T, void* W2N, hipStream_t stream);
+int dtfk_mlp_ipc_flag_bytes();
+hipError_t dtfk_mlp_ipc_reduce_apply(float* params, void* const* peer_table, int W, int rank, int parity,
+                                     long long slot_bytes, const long long* gstep, const float* lr, float scale,
+                                     void* W1T, void* W2T, void* W2N, int* err, long long timeout_ticks,
+                                     hipStream_t stream);
+// ---- mlp_gemm.hip
+int dtfk_mlpg_p1_floats();
+hipError_t dtfk_mlpg_fwd(const void* x, const void* labels, int B, int BP, const void* W1F, const float* params,
+                         float* a2g, float* P1, void* dz2F, int act, int naive, float gscale, hipStream_t s);
+int dtfk_mlpg_wchunk(int B);
+int dtfk_mlpg_p2_floats();
+hipError_t dtfk_mlpg_wgrad(const void* x, int B, const void* dz2F, float* P2, int nchunk, hipStream_t s);
+hipError_t dtfk_mlpg_apply(float* params, const float* P1, int n1, const float* P2, int n2, const float* gin,
+                           float* gout, const float* lr, float scale, void* W1S, float* metrics, int ring,
+                           long long* gstep, int B, int mode, hipStream_t s);
+// ---- mlp_persist_f32.hip
+void dtfk_mlpf_set_fault(int rank, long long step);
+long long dtfk_mlpf_stage_rec();
+long long dtfk_mlpf_xbuf_bytes();
+long long dtfk_mlpf_ipc_bytes();
+int dtfk_mlpf_max_batch();
+hipError_t dtfk_mlp_persist_f32_launch(const dtfk::mlpf::Launch* p, hipStream_t stream);
+// ---- graph_mlp.hip
+long long dtfk_graph_mlp_part_floats(int B, int H);
+hipError_t dtfk_graph_feed_ingest(const void* host, void* dev, long long bytes, hipStream_t stream);
+hipError_t dtfk_graph_mlp_step(const float* x, const uint8_t* xu, const float* ylab, float* W1, float* b1, float* W2,
+                               float* b2, float* a2buf, float* dz2buf, float* part, float* gW1, float* gb1,
+                               float* gW2, float* gb2, float* metrics, float* host_metrics, void* gstep,
+                               int gstep_kind, const float* lr_ptr, int B, int K, int H, int C, int act, int naive,
+                               int sgd, hipStream_t stream);
+}

@@ -34,6 +34,7 @@
 // array kept in scratch); a fused forward streaming all of W1 through every
 // workgroup was latency-chained over 7 k-step rounds.
 #include "common.h"
+#include "mlp_api.h"
 
 namespace dtfk {
 namespace mlpg {

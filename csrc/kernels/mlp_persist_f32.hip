@@ -74,11 +74,11 @@
 // the weights are written through to the graph's own variables and workgroup 0
 // publishes loss / accuracy / global_step and a done count to pinned memory.
 #include "common.h"
+#include "mlp_api.h"
 
 #include <atomic>
 
 #include <cstdlib>
-#include <cstring>
 
 namespace dtfk {
 namespace mlpf {
@@ -195,8 +195,6 @@ struct Args {
   int spread;               // placement: 0 packed on one XCD (default), 1 spread (several ranks per GPU)
   long long* phase_ts;      // optional phase stamps: [step < 64][workgroup 64][16] (wave 0 / wave 7, lane 0),
                             // then [64][workgroup 64][16] launch stamps (prologue / epilogue / copier)
-  int gmode;                // gather: 0 probe one granule per producer, then load; 1-3 direct loads with
-                            // no / short / long s_sleep between passes (DTF_GATHER_MODE, tuning)
   int xmode;                // N GPUs: 0 one-shot (every workgroup reads its slot from every peer),
                             // 1 two-shot (reduce-scatter by wave chunk, then all-gather of the sums)
   long long fault_step;     // fault injection (mlpf_set_fault(rank, step), tests of the bench's fallback):
@@ -226,8 +224,7 @@ struct Args {
   long long* res_ts;        // profiling only (DTF_RESIDENT_STAMPS): [run % 64][8] resident per-run stamps
   int dbg;                  // profiling only (DTF_PERSIST_DBG): bit 0 = never stage the next step's x (wrong
                             // numerics; what the per-step LDS-DMA stage costs the hand-offs), bit 1 = head
-                            // sub-phase stamps (slots 13-15, wave 0), bits 2 / 3 = stage (half) after the
-                            // first head, bit 4 = longer sleeps in the chunk polls (tuning)
+                            // sub-phase stamps (slots 13-15, wave 0)
 };
 
 // resident per-run stamp (s_memrealtime, 100 MHz) -- profiling only: 0 copier 0
@@ -362,18 +359,12 @@ __device__ __forceinline__ float xor32(float v) {
 // Gather the N granule slots slot(k) (k != skip) of this lane until every tag
 // matches; part[skip] = own (constant-index selects only: a runtime index would
 // demote the array to scratch).  `need` false: this lane takes no data (zeros;
-// it still joins the wave-wide exit test).  Polling is cheap: lane k < N watches
-// ONE granule of producer k (the last one lane `probe` writes) until it carries
-// the tag; only then does every lane load its own granules -- and re-loads the
-// few that were not there yet (no order between a producer's lanes).  A sweep
-// of every lane over every slot per poll was ~5 MB of L2 traffic per round.
-// false on timeout / error.
-// (gm: the poll mode -- 1, direct loads without sleeps, in production; the
-// instrumented instantiations take DTF_GATHER_MODE)
-template <int N, bool INS, typename SlotOff>
-__device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff slot, int skip, bool need, int probe,
-                                            unsigned tag, f32x4 own, f32x4 (&part)[N], int lane, const Args& a) {
-  const int gm = INS ? a.gmode : 1;
+// it still joins the wave-wide exit test).  Every lane loads its own granules
+// directly, pass after pass without sleeping, and re-loads only those that were
+// not there yet (no order between a producer's lanes).  false on timeout / error.
+template <int N, typename SlotOff>
+__device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff slot, int skip, bool need, unsigned tag,
+                                            f32x4 own, f32x4 (&part)[N], int lane, const Args& a) {
   bool have[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -381,24 +372,12 @@ __device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff s
     part[k] = (k == skip) ? own : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-  bool seen = lane >= N || lane == skip || gm != 0;
-  for (;;) {
-    asm volatile("" ::: "memory");   // re-load every pass (no loop-invariant hoisting)
-    if (!seen) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, slot(lane) + 32 * probe + 16, 0, 16);
-      seen = v[1] == tag && v[3] == tag;
-    }
-    if (__all(seen)) break;
-    if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > a.timeout ||
-        __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-      if (lane == 0) atomicOr(a.err, 1);
-      return false;
-    }
-  }
+  asm volatile("" ::: "memory");   // (redundant with the loop's; without it the relu NW = 4 f32-MFMA
+                                   // instantiation gets another register allocation)
   // the clock and the error word are checked every 8th pass only: a pass is one
   // L2 round trip, and the consumer CU's memory queue is what a hand-off waits on
   for (int it = 1;; ++it) {
-    asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");   // re-load every pass (no loop-invariant hoisting)
     bool all = true;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -406,8 +385,6 @@ __device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff s
       all = all && have[k];
     }
     if (__all(all)) return true;
-    if (gm == 2) __builtin_amdgcn_s_sleep(2);
-    else if (gm == 3) __builtin_amdgcn_s_sleep(8);
     if ((it & 7) == 0 && ((long long)__builtin_amdgcn_s_memrealtime() - t0 > a.timeout ||
                           __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
       if (lane == 0) atomicOr(a.err, 1);
@@ -698,18 +675,10 @@ __device__ void copier_res(const Args& a, int cid, uint8_t* smem) {
 // three-way split of their fp32 operand (pixels are exact in bf16), so every
 // product is exact and accumulates in fp32 -- 16x16x32 bf16 MFMAs at 8x the
 // f32-MFMA rate; the head stays on f32-input MFMA
-// EXP (timing experiment only, never the production instantiations; DTF_PERSIST_EXP,
-// scripts/probes/decomposition_sim.sh): the per-workgroup work of the 14- (EXP 2)
-// and 7-workgroup (EXP 4) decompositions on this 28-workgroup engine -- every
-// forward / weight-gradient MFMA chain and the next-step stage DMA run EXP times
-// (a 2x / 4x wider feature slice), E1 gathers 2 slices (EXP 2) or disappears
-// (EXP 4).  The sums are rescaled, so training still runs, but the numerics are
-// not the reference's: stamps and step times only.
-// INS: the instrumented build (phase stamps, DTF_PERSIST_DBG / DTF_GATHER_MODE
-// knobs) -- production instantiations carry none of that code
-template <int ACT, int NW, bool SPLIT, bool RES, int EXP = 0, bool INS = false>
+// INS: the instrumented build (phase / per-run stamps, the DTF_PERSIST_DBG
+// bits) -- production instantiations carry none of that code
+template <int ACT, int NW, bool SPLIT, bool RES, bool INS = false>
 __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) {
-  constexpr int XR = EXP > 1 ? EXP : 1;
   const int dbg = INS ? a.dbg : 0;
   constexpr bool MULTI = NW > 1;
   // w through readfirstlane: the compiler then knows it is wave-uniform, so the
@@ -1107,18 +1076,11 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
 #pragma unroll
         for (int b = 0; b < NBT; ++b) X[b] = px8(xf[0][b], xf[1][b]);
 #pragma unroll
-        for (int xr = 0; xr < XR; ++xr) {
+        for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Al, X[b], acc[b]);
 #pragma unroll
-          for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Al, X[b], acc[b]);
+        for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Am, X[b], acc[b]);
 #pragma unroll
-          for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Am, X[b], acc[b]);
-#pragma unroll
-          for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Ah, X[b], acc[b]);
-        }
-        if constexpr (XR > 1) {
-#pragma unroll
-          for (int b = 0; b < NBT; ++b) acc[b] *= 1.f / (float)XR;
-        }
+        for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Ah, X[b], acc[b]);
       } else {
 #pragma unroll
         for (int k = 0; k < NTW; ++k) {
@@ -1146,16 +1108,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       return (unsigned)__ballot(ok) & ((1u << NBT) - 1u);
     };
     if (w == 7 && more && !(dbg & 1)) {
-      // DTF_PERSIST_DBG bits 2 / 3 (tuning): the whole stage / its second half only
-      // once the first head is done (its DMA then does not queue in front of this
-      // CU's E1 / E2 gather loads)
-      if (dbg & 8) stage_x(st + 1, 0, 2);
-      if (dbg & 12) {
-        while (heads_done() == 0u) __builtin_amdgcn_s_sleep(1);
-      }
-      if (dbg & 8) stage_x(st + 1, 1, 2);
-      else
-        for (int xr = 0; xr < XR; ++xr) stage_x(st + 1, 0, 1);
+      stage_x(st + 1, 0, 1);
       // idle until the first head is done anyway: wait for the DMA here and tell the
       // other waves the next step's operands are in LDS
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1175,7 +1128,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       // publish the slice partial of (j, batch tile w) as granules; gather the others
       // E1 region of (parity, block j): [slice][batch tile] slots
       const auto r1 = region_rsrc(a.xbuf + E1_OFF + (long long)(par * NJ + j) * NQ * NBT * GSLOT, NQ * NBT * GSLOT);
-      if constexpr (EXP != 4) put_gran(r1, (q * NBT + w) * GSLOT + 32 * lane, zs, tag, l2_e1);
+      put_gran(r1, (q * NBT + w) * GSLOT + 32 * lane, zs, tag, l2_e1);
       if (w == 0) { PH(3); }
       // this step's W2 / b1 / b2 operands of the lane, read from LDS while the
       // partial is in flight (their LDS latency off the E1 -> P1 -> E2 -> head chain)
@@ -1187,23 +1140,11 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         b1v[e] = b1s[4 * g + e];
         b2v[e] = b2s[4 * g + e];
       }
-      f32x4 z;
-      bool ok = true;
-      if constexpr (EXP == 4) {
-        z = zs * 4.f;
-      } else if constexpr (EXP == 2) {
-        f32x4 part[2];
-        ok = gather_gran<2, INS>(r1, [&](int k) { return (((q & 2) + k) * NBT + w) * GSLOT; }, q & 1, true, 63, tag, zs, part,
-                            lane, a);
-        z = (part[0] + part[1]) * 2.f;
-      } else {
-        f32x4 part[NQ];
-        ok = gather_gran<NQ, INS>(r1, [&](int k) { return (k * NBT + w) * GSLOT; }, jq[1], true, 63, tag, zs, part, lane,
-                                  a);
-        z = part[0];
+      f32x4 part[NQ];
+      bool ok = gather_gran<NQ>(r1, [&](int k) { return (k * NBT + w) * GSLOT; }, jq[1], true, tag, zs, part, lane, a);
+      f32x4 z = part[0];
 #pragma unroll
-        for (int qq = 1; qq < NQ; ++qq) z += part[qq];
-      }
+      for (int qq = 1; qq < NQ; ++qq) z += part[qq];
       if (w == 0) { PH(4); }
       if (w == 0) { PH(5); }
       // lane (batch r, g): hidden 16j+4g+i
@@ -1229,7 +1170,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
 #pragma unroll
       for (int i = 0; i < 4; ++i) a2T[(4 * g + i) * LS + bw] = a2[i];
       f32x4 lp[NJ];
-      ok = gather_gran<NJ, INS>(r2, [&](int k) { return k * GSLOT; }, jq[0], g < 3, 47, tag, pl, lp, lane, a) && ok;
+      ok = gather_gran<NJ>(r2, [&](int k) { return k * GSLOT; }, jq[0], g < 3, tag, pl, lp, lane, a) && ok;
       if (w == 0) { PH(7); }
       if (!ok && lane == 0) *abort_flag = 1;
       // logits, softmax cross-entropy, accuracy -- identical in every workgroup
@@ -1391,26 +1332,18 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
           if (ch == cc && (hm & need_of(ch)) == need_of(ch)) {   // wave-uniform
             if (!did) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
             if (cc == 0 && w == 0) { PH(10); }
-#pragma unroll
-            for (int xr = 0; xr < XR; ++xr) chunk(ch);
+            chunk(ch);
             ++cc;
             did = true;
           }
         }
         if (cc == NCH) break;
-        if (!did) {
-          if (dbg & 16) __builtin_amdgcn_s_sleep(2);
-          else __builtin_amdgcn_s_sleep(0);
-        }
+        if (!did) __builtin_amdgcn_s_sleep(0);
       }
     }
     if constexpr (!SPLIT) {
 #pragma unroll
       for (int k = 0; k < NTW; ++k) G[k] = G[k] + G1[k];
-    }
-    if constexpr (XR > 1) {
-#pragma unroll
-      for (int k = 0; k < NTW; ++k) G[k] *= 1.f / (float)XR;
     }
     // every head is done here.  Wave 7 sums the 7 head waves' dW2 / db2 partials
     // and the per-row metrics in fixed order (all loads in flight at once); one
@@ -1708,7 +1641,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
 // L2); the first NCOP other blocks copy, the rest exit.  spread (several ranks on
 // one GPU, tests): compute = blocks 0..27, copiers = 28..43.  Placement is speed
 // only: the census above decides each edge's store flavour.
-template <int ACT, int NW, bool SPLIT, bool RES = false, int EXP = 0, bool INS = false>
+template <int ACT, int NW, bool SPLIT, bool RES = false, bool INS = false>
 __global__ __launch_bounds__(THREADS, 1) void mlp_persist_f32(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int b = blockIdx.x;
@@ -1719,16 +1652,14 @@ __global__ __launch_bounds__(THREADS, 1) void mlp_persist_f32(Args a) {
     if ((b & 7) == 0) c = b >> 3; else cid = b - (b >> 3) - 1;
   }
   if (c >= 0) {
-    if (a.nsteps > 0) compute<ACT, NW, SPLIT, RES, EXP, INS>(a, c / NQ, c % NQ, smem);
+    if (a.nsteps > 0) compute<ACT, NW, SPLIT, RES, INS>(a, c / NQ, c % NQ, smem);
     return;
   }
   if constexpr (RES) copier_res(a, cid, smem);
   else if (cid < NCOP) copier(a, cid, smem);
 }
 
-}  // namespace mlpf
-}  // namespace dtfk
-
+// ------------------------------------------------------------------ host launch
 // fault injection (tests of the bench's in-process fallback): rank `rank` stops
 // publishing its exchange flag from global step `step` on; rank -1 = off
 static int g_fault_rank = -1;
@@ -1742,226 +1673,143 @@ static unsigned next_census_tag() {
   return t == 0u ? ctr.fetch_add(1u, std::memory_order_relaxed) + 1u : t;
 }
 
+// DTF_PERSIST_DBG (profiling, flat launches), read once per process: a getenv per
+// launch is host time inside a short timed run
+static int persist_dbg() {
+  static const int dbg = [] {
+    const char* db = getenv("DTF_PERSIST_DBG");
+    return db ? atoi(db) : 0;
+  }();
+  return dbg;
+}
+
+// The kernel's arguments of one launch: every field from `p` or zero.
+static Args make_args(const Launch& p) {
+  const bool res = p.door != nullptr;
+  Args a{};
+  a.stage = static_cast<const uint8_t*>(p.stage);
+  a.rec_h = p.rec_h;
+  a.B = p.B;
+  a.nsteps = res ? 0x7fffffff : p.nsteps;   // resident: bounded by the doorbell / idle exit
+  a.params = p.params;
+  a.lr = p.lr;
+  a.metrics = p.metrics;
+  a.ring = p.ring;
+  a.act = p.act;
+  a.naive = p.naive;
+  a.gstep = p.gstep;
+  a.seq = p.seq;
+  a.xbuf = static_cast<uint8_t*>(p.xbuf);
+  a.err = p.err;
+  a.timeout = p.timeout;
+  a.step_ts = p.step_ts;
+  a.ts_ring = p.ts_ring > 0 ? p.ts_ring : 1;
+  a.host_next = static_cast<const uint8_t*>(p.host_next);
+  a.next_steps = p.next_steps;
+  a.stage_next = static_cast<uint8_t*>(p.stage_next);
+  a.peer_base = p.peer_base;
+  a.W = p.W;
+  a.rank = p.rank;
+  a.gbf16 = p.gbf16;
+  a.spread = p.spread;
+  a.phase_ts = p.phase_ts;
+  a.xmode = p.xmode;
+  a.fault_step = g_fault_step;
+  a.fault_rank = g_fault_rank;
+  a.p_w2 = p.W2 != nullptr ? p.W2 : p.params + OFF_W2;
+  a.p_b1 = p.b1 != nullptr ? p.b1 : p.params + OFF_B1;
+  a.p_b2 = p.b2 != nullptr ? p.b2 : p.params + OFF_B2;
+  a.door = p.door;
+  a.host_recs = static_cast<const uint8_t*>(p.host_recs);
+  a.host_lr = p.host_lr;
+  a.host_out = p.host_out;
+  a.host_done = p.host_done;
+  a.host_state = p.host_state;
+  a.launch_id = p.launch_id;
+  a.run0 = p.run0;
+  a.idle = p.idle;
+  a.census_tag = next_census_tag();
+  a.gvar = p.gvar;
+  a.gvar_kind = p.gvar_kind;
+  a.dctr = p.dctr;
+  a.res_ts = p.res_ts;
+  a.dbg = res ? 0 : persist_dbg();
+  return a;
+}
+
+typedef void (*Kern)(Args);
+// every instantiation the launcher can pick: [0, 16) production, act + 2 nwi + 8 split
+// (NW, the peer-table width the exchange is unrolled for: 1, 2, 4, 8); [16, 20)
+// instrumented, act + 2 split; [20, 24) resident, act + 2 instrumented
+static const Kern kKernels[24] = {
+    mlp_persist_f32<0, 1, false>, mlp_persist_f32<1, 1, false>, mlp_persist_f32<0, 2, false>,
+    mlp_persist_f32<1, 2, false>, mlp_persist_f32<0, 4, false>, mlp_persist_f32<1, 4, false>,
+    mlp_persist_f32<0, 8, false>, mlp_persist_f32<1, 8, false>, mlp_persist_f32<0, 1, true>,
+    mlp_persist_f32<1, 1, true>,  mlp_persist_f32<0, 2, true>,  mlp_persist_f32<1, 2, true>,
+    mlp_persist_f32<0, 4, true>,  mlp_persist_f32<1, 4, true>,  mlp_persist_f32<0, 8, true>,
+    mlp_persist_f32<1, 8, true>,
+    mlp_persist_f32<0, 1, false, false, true>, mlp_persist_f32<1, 1, false, false, true>,
+    mlp_persist_f32<0, 1, true, false, true>,  mlp_persist_f32<1, 1, true, false, true>,
+    mlp_persist_f32<0, 1, true, true>,         mlp_persist_f32<1, 1, true, true>,
+    mlp_persist_f32<0, 1, true, true, true>,   mlp_persist_f32<1, 1, true, true, true>};
+
+// The instantiation for (activation, NW index, split, resident, instrumented);
+// nullptr where none exists: the instrumented build is one-GPU only, the
+// resident engine split and one-GPU only.
+static Kern select_kernel(int act, int nwi, bool split, bool res, bool ins) {
+  const int ai = act == 0 ? 0 : 1;
+  if (res) return (split && nwi == 0) ? kKernels[20 + ai + (ins ? 2 : 0)] : nullptr;
+  if (ins) return nwi == 0 ? kKernels[16 + ai + (split ? 2 : 0)] : nullptr;
+  return kKernels[ai + 2 * nwi + (split ? 8 : 0)];
+}
+
+}  // namespace mlpf
+}  // namespace dtfk
+
 extern "C" {
 
 void dtfk_mlpf_set_fault(int rank, long long step) {
-  g_fault_rank = rank;
-  g_fault_step = step;
+  dtfk::mlpf::g_fault_rank = rank;
+  dtfk::mlpf::g_fault_step = step;
 }
-
-// profiling only: the resident launches' per-run stamp ring (nullptr: off)
-static long long* g_res_ts = nullptr;
-void dtfk_mlpf_set_res_ts(long long* p) { g_res_ts = p; }
 
 long long dtfk_mlpf_stage_rec() { return dtfk::mlpf::REC; }
 long long dtfk_mlpf_xbuf_bytes() { return dtfk::mlpf::XBUF_BYTES; }
 long long dtfk_mlpf_ipc_bytes() { return dtfk::mlpf::IPC_BYTES; }
 int dtfk_mlpf_max_batch() { return dtfk::mlpf::BROWS; }
 
-typedef void (*Kern2)(dtfk::mlpf::Args);
-hipError_t dtfk_mlp_persist_f32(const void* stage, long long rec_h, int B, int nsteps, float* params, const float* lr,
-                                float* metrics, int ring, int act, int naive, long long* gstep, unsigned long long* seq,
-                                void* xbuf, int* err, long long timeout, long long* step_ts, int ts_ring,
-                                const void* host_next, int next_steps, void* stage_next, void* const* peer_base, int W,
-                                int rank, int gbf16, long long* phase_ts, int spread, int xmode, int split,
-                                hipStream_t stream) {
-  using namespace dtfk::mlpf;
-  Args a;
-  a.phase_ts = phase_ts;
-  a.res_ts = nullptr;
-  a.stage = static_cast<const uint8_t*>(stage);
-  a.rec_h = rec_h;
-  a.B = B;
-  a.nsteps = nsteps;
-  a.params = params;
-  a.p_w2 = params + OFF_W2;
-  a.p_b1 = params + OFF_B1;
-  a.p_b2 = params + OFF_B2;
-  a.door = nullptr;
-  a.host_recs = nullptr;
-  a.host_lr = nullptr;
-  a.host_out = nullptr;
-  a.host_done = nullptr;
-  a.host_state = nullptr;
-  a.launch_id = a.run0 = a.idle = 0;
-  a.census_tag = next_census_tag();
-  a.gvar = nullptr;
-  a.gvar_kind = 0;
-  a.dctr = nullptr;
-  a.lr = lr;
-  a.metrics = metrics;
-  a.ring = ring;
-  a.act = act;
-  a.naive = naive;
-  a.gstep = gstep;
-  a.seq = seq;
-  a.xbuf = static_cast<uint8_t*>(xbuf);
-  a.err = err;
-  a.timeout = timeout;
-  a.step_ts = step_ts;
-  a.ts_ring = ts_ring > 0 ? ts_ring : 1;
-  a.host_next = static_cast<const uint8_t*>(host_next);
-  a.next_steps = next_steps;
-  a.stage_next = static_cast<uint8_t*>(stage_next);
-  a.peer_base = peer_base;
-  a.W = W;
-  a.rank = rank;
-  a.gbf16 = gbf16;
-  a.spread = spread;
-  a.xmode = xmode;
-  {
-    // read once per process (a getenv per launch is host time inside a short timed run)
-    static const int gmode = [] {
-      const char* gm = getenv("DTF_GATHER_MODE");   // r3: direct loads, no sleep 8.68 / long sleep 8.72 / probe 9.56 us
-      return gm ? atoi(gm) : 1;
-    }();
-    static const int dbg = [] {
-      const char* db = getenv("DTF_PERSIST_DBG");
-      return db ? atoi(db) : 0;
-    }();
-    a.gmode = gmode;
-    a.dbg = dbg;
-    // timing experiment only (see compute's EXP): 2 / 4 = the 14- / 7-workgroup
-    // decompositions' per-workgroup work, sigmoid one-GPU split engine only
-    static const int exper = [] {
-      const char* e = getenv("DTF_PERSIST_EXP");
-      return e ? atoi(e) : 0;
-    }();
-    if (exper == 2 || exper == 4) {
-      if (act != 0 || W != 1 || !split || spread) return hipErrorInvalidValue;
-      static const Kern2 xk[2] = {mlp_persist_f32<0, 1, true, false, 2, true>,
-                                  mlp_persist_f32<0, 1, true, false, 4, true>};
-      const Kern2 k = xk[exper == 2 ? 0 : 1];
-      static bool xattr = false;
-      if (!xattr) {
-        for (Kern2 kk : xk) {
-          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kk),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-          if (e != hipSuccess) return e;
-        }
-        xattr = true;
-      }
-      hipLaunchKernelGGL(k, dim3(GRID_PACKED), dim3(THREADS), LDS_BYTES, stream, a);
-      return hipGetLastError();
-    }
-    a.fault_rank = g_fault_rank;
-    a.fault_step = g_fault_step;
-  }
-  constexpr size_t lds = LDS_BYTES;
-  typedef void (*Kern)(Args);
-  // NW: peer-table width the exchange is unrolled for (W rounded up to 2 / 4 / 8)
-  static const Kern kerns[16] = {
-      mlp_persist_f32<0, 1, false>, mlp_persist_f32<1, 1, false>, mlp_persist_f32<0, 2, false>,
-      mlp_persist_f32<1, 2, false>, mlp_persist_f32<0, 4, false>, mlp_persist_f32<1, 4, false>,
-      mlp_persist_f32<0, 8, false>, mlp_persist_f32<1, 8, false>, mlp_persist_f32<0, 1, true>,
-      mlp_persist_f32<1, 1, true>,  mlp_persist_f32<0, 2, true>,  mlp_persist_f32<1, 2, true>,
-      mlp_persist_f32<0, 4, true>,  mlp_persist_f32<1, 4, true>,  mlp_persist_f32<0, 8, true>,
-      mlp_persist_f32<1, 8, true>};
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (Kern k : kerns) {
-      const hipError_t e =
-          hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    attr_set = true;
-  }
-  if (W < 1 || W > 8 || rank < 0 || rank >= W) return hipErrorInvalidValue;
-  const int nwi = W <= 1 ? 0 : (W <= 2 ? 1 : (W <= 4 ? 2 : 3));
-  const int which = (act == 0 ? 0 : 1) + 2 * nwi + (split ? 8 : 0);
-  const int grid = spread ? GRID_SPREAD : GRID_PACKED;
-  if (phase_ts != nullptr || a.dbg != 0 || a.gmode != 1) {
-    // profiling / tuning: the instrumented build (one GPU only)
-    if (W != 1) return hipErrorInvalidValue;
-    static const Kern ik[4] = {mlp_persist_f32<0, 1, false, false, 0, true>, mlp_persist_f32<1, 1, false, false, 0, true>,
-                               mlp_persist_f32<0, 1, true, false, 0, true>, mlp_persist_f32<1, 1, true, false, 0, true>};
-    static bool iattr = false;
-    if (!iattr) {
-      for (Kern k : ik) {
-        const hipError_t e =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-      }
-      iattr = true;
-    }
-    hipLaunchKernelGGL(ik[(act == 0 ? 0 : 1) + (split ? 2 : 0)], dim3(grid), dim3(THREADS), lds, stream, a);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(kerns[which], dim3(grid), dim3(THREADS), lds, stream, a);
-  return hipGetLastError();
-}
-
-// The resident Session engine (compat/resident.py, csrc/bind_mlp.cpp
+// One launch of the engine.  Flat (p->door == nullptr): `nsteps` SGD steps of the
+// chunk in `stage` on the flat master and, in the same launch, `next_steps` host
+// records into `stage_next`.  Resident (compat/resident.py, csrc/bind_mlp.cpp
 // ResidentMLPPlan): ONE launch serves Session.run calls until `idle` ticks pass
-// without a doorbell or the host writes door < 0.  One GPU, the reference's
+// without a doorbell or the host writes door < 0 -- one GPU, the reference's
 // precision (SPLIT), packed placement; the graph's own W1 / W2 / b1 / b2 tensors
 // and global_step variable are read at launch and written through every step.
-hipError_t dtfk_mlp_persist_f32_resident(void* stage, int B, float* W1, float* W2, float* b1, float* b2, const float* lr,
-                                         float* metrics, int ring, int act, int naive, long long* gstep,
-                                         unsigned long long* seq, void* xbuf, int* err, long long timeout,
-                                         const long long* door, const void* host_recs, long long rec_h,
-                                         const float* host_lr, float* host_out, long long* host_done,
-                                         long long* host_state, long long launch_id, long long run0, long long idle,
-                                         void* gvar, int gvar_kind, unsigned* dctr, hipStream_t stream) {
+// Instrumented instantiations (profiling): flat with phase stamps or
+// DTF_PERSIST_DBG, resident with per-run stamps.
+hipError_t dtfk_mlp_persist_f32_launch(const dtfk::mlpf::Launch* p, hipStream_t stream) {
   using namespace dtfk::mlpf;
-  if (B < 1 || B > BROWS || rec_h < (long long)B * (DIN + 1) || gvar_kind < 0 || gvar_kind > 4 ||
-      (gvar_kind != 0 && gvar == nullptr))
+  const bool res = p->door != nullptr;
+  if (p->B < 1 || p->B > BROWS || p->rec_h < (long long)p->B * (DIN + 1) || p->gvar_kind < 0 || p->gvar_kind > 4 ||
+      (p->gvar_kind != 0 && p->gvar == nullptr))
     return hipErrorInvalidValue;
-  Args a;
-  std::memset(&a, 0, sizeof(a));
-  a.stage = static_cast<const uint8_t*>(stage);
-  a.rec_h = rec_h;
-  a.B = B;
-  a.nsteps = 0x7fffffff;   // bounded by the doorbell / idle exit
-  a.params = W1;
-  a.p_w2 = W2;
-  a.p_b1 = b1;
-  a.p_b2 = b2;
-  a.lr = lr;
-  a.metrics = metrics;
-  a.ring = ring;
-  a.act = act;
-  a.naive = naive;
-  a.gstep = gstep;
-  a.seq = seq;
-  a.xbuf = static_cast<uint8_t*>(xbuf);
-  a.err = err;
-  a.timeout = timeout;
-  a.ts_ring = 1;
-  a.W = 1;
-  a.gmode = 1;
-  a.fault_rank = -1;
-  a.fault_step = -1;
-  a.door = door;
-  a.host_recs = static_cast<const uint8_t*>(host_recs);
-  a.host_lr = host_lr;
-  a.host_out = host_out;
-  a.host_done = host_done;
-  a.host_state = host_state;
-  a.launch_id = launch_id;
-  a.census_tag = next_census_tag();
-  a.run0 = run0;
-  a.idle = idle;
-  a.gvar = gvar;
-  a.gvar_kind = gvar_kind;
-  a.dctr = dctr;
-  a.res_ts = g_res_ts;
-  constexpr size_t lds = LDS_BYTES;
-  typedef void (*Kern)(Args);
-  // per-run stamps (DTF_RESIDENT_STAMPS): the instrumented build
-  static const Kern kerns[4] = {mlp_persist_f32<0, 1, true, true>, mlp_persist_f32<1, 1, true, true>,
-                                mlp_persist_f32<0, 1, true, true, 0, true>, mlp_persist_f32<1, 1, true, true, 0, true>};
+  if (p->W < 1 || p->W > 8 || p->rank < 0 || p->rank >= p->W) return hipErrorInvalidValue;
+  if (res && p->spread) return hipErrorInvalidValue;
   static bool attr_set = false;
   if (!attr_set) {
-    for (Kern k : kerns) {
-      const hipError_t e =
-          hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (Kern k : kKernels) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
       if (e != hipSuccess) return e;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL(kerns[(act == 0 ? 0 : 1) + (a.res_ts != nullptr ? 2 : 0)], dim3(GRID_PACKED), dim3(THREADS), lds,
-                     stream, a);
+  const Args a = make_args(*p);
+  const int nwi = p->W <= 1 ? 0 : (p->W <= 2 ? 1 : (p->W <= 4 ? 2 : 3));
+  const bool ins = res ? p->res_ts != nullptr : (p->phase_ts != nullptr || a.dbg != 0);
+  const Kern k = select_kernel(p->act, nwi, p->split != 0, res, ins);
+  if (k == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(p->spread ? GRID_SPREAD : GRID_PACKED), dim3(THREADS), LDS_BYTES, stream, a);
   return hipGetLastError();
 }
 

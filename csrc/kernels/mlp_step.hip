@@ -46,6 +46,7 @@
 // bf16 shadows: W1T [112][800] (n-major, k contiguous), W2T [16][128] (class-
 // major, hidden contiguous), W2N [112][32] (hidden-major, class contiguous).
 #include "common.h"
+#include "mlp_api.h"
 
 namespace dtfk {
 namespace mlp {

@@ -635,7 +635,7 @@ class PersistentMLPRunner:
         self.seq = torch.zeros(1, dtype=torch.int64, device=dev)
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
         self.step_ts = torch.zeros(self.TS_RING, dtype=torch.int64, device=dev)
-        self.phase_ts = None    # fp32 engine: optional [64 steps][64 wg][16] phase stamps (profiling)
+        self._phase_ts = None   # fp32 engine: optional [64 steps][64 wg][16] phase stamps (profiling): `phase_ts`
         self._plan = None       # fp32 engine: prepared C++ launcher (PersistF32Plan)
         self.cursor = 0
         self.staged: List[Optional[Tuple[int, int]]] = [None, None]   # (b0, g) resident per stage buffer
@@ -653,6 +653,18 @@ class PersistentMLPRunner:
             self.ipc = open_peer_buffers(C, int(C.mlpf_ipc_bytes()), w)
             self.W, self.rank = w.world_size, w.rank
 
+    @property
+    def phase_ts(self):
+        return self._phase_ts
+
+    @phase_ts.setter
+    def phase_ts(self, ts):
+        """Phase stamps on (an int64 [65*64*16] device tensor: the launches then run
+        the instrumented build) or off (None)."""
+        if self._plan is not None:
+            self._plan.set_phase_ts(ts)
+        self._phase_ts = ts
+
     def _chunks(self, cursor: int, steps: int) -> List[Tuple[int, int]]:
         out, left = [], steps
         nb = self.epoch.num_batches
@@ -667,26 +679,16 @@ class PersistentMLPRunner:
     def _launch(self, par: int, off: int, nsteps: int, nxt: Tuple[int, int]):
         """Run `nsteps` from stage `par` at step offset `off`; copy `nxt` into stage par^1."""
         t, ep = self.t, self.epoch
-        dst = par ^ 1
-        ipc = dict(ipc_table=self.ipc.table_ptr() if self.ipc is not None else 0, ipc_W=self.W, ipc_rank=self.rank)
-        if self.phase_ts is None:
-            if self._plan is None:   # every pointer resolved once (host-side launch cost)
-                self._plan = t.C.PersistF32Plan(
-                    self.stages[0], self.stages[1], ep.rec, t.B, t.params, t.lr, t.metrics, t.gstep, self.seq,
-                    self.xbuf, self.err, self.timeout_s, t.act, int(t.naive), ep.host, self.step_ts,
-                    ipc["ipc_table"], self.W, self.rank, self.grad_bf16, self.placement == "spread",
-                    self.exchange == "two-shot", self.mfma_split)
-            self._plan.launch(par, off if nsteps > 0 else 0, nsteps, nxt[0] * ep.rec, nxt[1])
-        else:   # phase stamps (profiling): the generic binding
-            st = self.stages[par][off * self.rec_s:] if nsteps > 0 else self.stages[par]
-            t.C.mlp_persist_f32(st, ep.rec, t.B, nsteps, t.params, t.lr, t.metrics, t.gstep, self.seq, self.xbuf,
-                                self.err, self.timeout_s, t.act, int(t.naive), host=ep.host,
-                                host_offset=nxt[0] * ep.rec, next_steps=nxt[1], stage_next=self.stages[dst],
-                                step_ts=self.step_ts, grad_bf16=self.grad_bf16, phase_ts=self.phase_ts,
-                                spread=self.placement == "spread", two_shot=self.exchange == "two-shot",
-                                mfma_split=self.mfma_split, **ipc)
+        if self._plan is None:   # every pointer resolved once (host-side launch cost)
+            self._plan = t.C.PersistF32Plan(
+                self.stages[0], self.stages[1], ep.rec, t.B, t.params, t.lr, t.metrics, t.gstep, self.seq,
+                self.xbuf, self.err, self.timeout_s, t.act, int(t.naive), ep.host, self.step_ts,
+                self.ipc.table_ptr() if self.ipc is not None else 0, self.W, self.rank, self.grad_bf16,
+                self.placement == "spread", self.exchange == "two-shot", self.mfma_split)
+            self._plan.set_phase_ts(self._phase_ts)
+        self._plan.launch(par, off if nsteps > 0 else 0, nsteps, nxt[0] * ep.rec, nxt[1])
         if nxt[1] > 0:
-            self.staged[dst] = nxt
+            self.staged[par ^ 1] = nxt
         self.last_prefetch_steps = nxt[1]
 
     def _locate(self, b0: int, g: int) -> Optional[Tuple[int, int]]:
@@ -752,7 +754,7 @@ class PersistentMLPRunner:
         Same launch and bookkeeping as the general path; False when it does not apply."""
         nb = self.epoch.num_batches
         b0 = self.cursor % nb
-        if steps <= 0 or steps > self.g or b0 + steps > nb or self.phase_ts is not None:
+        if steps <= 0 or steps > self.g or b0 + steps > nb or self._phase_ts is not None:
             return False
         s0, s1 = self.staged
         if s0 is not None and s0[0] <= b0 and b0 + steps <= s0[0] + s0[1]:

@@ -17,8 +17,8 @@
 #   bench5500     bench.py defaults (10 epochs of 550 steps)
 #   bench2        bench.py --gpus 2 as the driver launches it, both ranks on cuda:0
 #   phases        per-phase device stamps of the fp32 engine (scripts/prof_persist_f32.py)
-#   phase_sweep   the same under each "DBG:GATHER" pair of $PHASE_SWEEP (DTF_PERSIST_DBG /
-#                 DTF_GATHER_MODE kernel knobs; default "0:3 1:3 0:0 0:1")
+#   phase_sweep   the same under each DTF_PERSIST_DBG value of $PHASE_SWEEP (the instrumented
+#                 build's bits: 1 never stage, 2 head sub-phase stamps; default "0 1")
 #   prof_bench    rocprofv3 kernel trace + stats of bench.py --steps 5500
 #   lowering      compat-graph lowering tests + bench_graph_step
 #   models        BERT-base / ResNet-50 / sparse benches (scripts/bench_models.py)
@@ -69,9 +69,8 @@ for step in "$@"; do
         --master-addr=127.0.0.1 --master-port=$PORT bench.py --gpus 2 --steps 20 --warmup 5 $extra ;;
     phases) run phases 300 python scripts/prof_persist_f32.py fp32 $extra ;;
     phase_sweep)
-      for pair in ${PHASE_SWEEP:-0:3 1:3 0:0 0:1}; do
-        DTF_PERSIST_DBG=${pair%%:*} DTF_GATHER_MODE=${pair##*:} run phases_${pair%%:*}_${pair##*:} 300 \
-          python scripts/prof_persist_f32.py fp32 $extra
+      for dbg in ${PHASE_SWEEP:-0 1}; do
+        DTF_PERSIST_DBG=$dbg run phases_$dbg 300 python scripts/prof_persist_f32.py fp32 $extra
       done ;;
     prof_bench)
       rm -rf $OUT/prof_bench

@@ -85,6 +85,42 @@ def test_persist_f32_multi_step_matches_reference(native, engine):
     assert np.allclose(m[:, 1], accs, atol=1e-6)
 
 
+@pytest.mark.parametrize("engine", ["fp32", "fp32-mfma"])
+def test_persist_f32_instrumented_build_through_the_plan(native, engine):
+    """Phase stamps on: the plan launches the instrumented instantiation, which
+    computes the same 3 steps (B = 37: a partial last batch tile) and stamps every
+    phase of every compute workgroup; stamps off: back to the production kernel."""
+    B, nb = 37, 6
+    imgs, labels = synthetic_mnist(B * nb, seed=16)
+    dev = torch.device("cuda")
+    lr = 0.05
+    tr = mlp.FusedMLPTrainer(batch_size=B, lr=lr, device=dev)
+    p0 = tr.get_params().clone()
+    ep = PinnedEpoch(imgs, labels, B)
+    run = mlp.PersistentMLPRunner(tr, ep, steps_per_launch=4, precision=engine)
+    ts = torch.zeros(65 * 64 * 16, dtype=torch.int64, device=dev)
+    run.phase_ts = ts
+    run.run(3)     # (0,3): cold copy, then ONE 3-step launch
+    torch.cuda.synchronize()
+    assert run.error() == 0
+    assert tr.global_step == 3
+    p_ref, _, _ = _ref_run(p0, imgs, labels, B, [0, 1, 2], lr)
+    d_k = tr.get_params().double() - p0.double()
+    d_r = p_ref.double() - p0.double()
+    rel = ((d_k - d_r).norm() / d_r.norm()).item()
+    assert rel < 2e-5, rel
+    s = ts.cpu().numpy().reshape(65, 64, 16)
+    ph = s[:3, :28, :13]          # steps 0..2, compute workgroups 0..27, wave 0's phase slots
+    assert (ph != 0).all()
+    assert (np.diff(ph, axis=2) >= 0).all()
+    assert (s[64, :28, 0] != 0).all() and (s[64, :28, 5] != 0).all()   # launch row: start / end of compute
+    run.phase_ts = None
+    run.run(2)
+    torch.cuda.synchronize()
+    assert run.error() == 0
+    assert tr.global_step == 5
+
+
 @pytest.mark.parametrize("precision", ["fp32", "fp32-mfma"])
 def test_persist_short_timed_run_streams_only_what_it_computes(native, precision):
     """The bench's pattern: warmup(5) primes exactly the timed run's chunk; the

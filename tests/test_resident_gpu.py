@@ -42,8 +42,13 @@ def _check_steps(tf, sess, g, params, batches, lr, act="sigmoid", stable=False, 
     return params
 
 
-@pytest.mark.parametrize("stable,act,B", [(False, "sigmoid", 100), (True, "relu", 64), (False, "sigmoid", 112)])
-def test_resident_steps_match_fp64(monkeypatch, stable, act, B):
+@pytest.mark.parametrize("stable,act,B", [(False, "sigmoid", 100), (True, "relu", 64), (False, "sigmoid", 112),
+                                          pytest.param(False, "sigmoid", 100, id="stamps")])
+def test_resident_steps_match_fp64(monkeypatch, request, stable, act, B):
+    """Case "stamps": the same steps on the instrumented resident build (per-run stamps on)."""
+    stamps = request.node.callspec.id == "stamps"
+    if stamps:
+        monkeypatch.setenv("DTF_RESIDENT_STAMPS", "1")
     monkeypatch.setenv("DTF_RESIDENT_IDLE_S", "2.0")
     import distributed_tensorflow_example_amd.compat as tf
     from distributed_tensorflow_example_amd.compat import lowering as L
@@ -58,6 +63,11 @@ def test_resident_steps_match_fp64(monkeypatch, stable, act, B):
         _check_steps(tf, sess, g, params, batches, 0.5, act, stable)
         plan = L.plan_for(g["train"])
         assert plan.resident_steps == 6 and plan._rplan.plan.launches() == 1
+        if stamps:
+            plan._rplan.stop()                  # the launch has ended: its last stamps are in memory
+            st = plan._rplan.plan.stamps()
+            assert st is not None
+            assert (st[0].numpy().reshape(64, 8)[:6] != 0).all()   # runs 0..5, all 8 stamps of each
     tf.reset_default_graph()
 
 
