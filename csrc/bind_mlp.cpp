@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "comm/ipc_coll_host.h"
+#include "gstep_host.h"
 #include "kernels/mlp_api.h"
 
 #include <algorithm>
@@ -393,18 +394,6 @@ struct PersistF32Plan {
   }
 };
 
-static int gstep_kind_of(const at::Tensor& g) {
-  TORCH_CHECK(g.is_cuda() && g.numel() == 1, "graph_mlp_step: device scalar global_step");
-  switch (g.scalar_type()) {
-    case at::kFloat: return 0;
-    case at::kLong: return 1;
-    case at::kInt: return 2;
-    case at::kDouble: return 3;
-    default: TORCH_CHECK(false, "graph_mlp_step: unsupported global_step dtype");
-  }
-  return 0;
-}
-
 // The compat graph's matched MLP training step (csrc/kernels/graph_mlp.hip).
 // sgd: W/b updated in place with lr; else gradients into g* (same shapes).
 void graph_mlp_step(at::Tensor x, at::Tensor ylab, at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2,
@@ -423,11 +412,11 @@ void graph_mlp_step(at::Tensor x, at::Tensor ylab, at::Tensor W1, at::Tensor b1,
   const int HP = (H + 16) & ~15, BP = (B + 15) & ~15;
   TORCH_CHECK(a2buf.numel() >= (int64_t)BP * HP && dz2buf.numel() >= (int64_t)BP * HP && metrics.numel() >= 3,
               "graph_mlp_step: scratch too small");
-  float *gW1 = nullptr, *gb1 = nullptr, *gW2 = nullptr, *gb2 = nullptr;
+  dtfk::gmlp::Step p{};
   if (!sgd) {
     TORCH_CHECK(grads.has_value() && grads->size() == 4, "graph_mlp_step: gradients [dW1, db1, dW2, db2] expected");
     const int64_t n[4] = {(int64_t)K * H, H, (int64_t)H * C, C};
-    float** dst[4] = {&gW1, &gb1, &gW2, &gb2};
+    float** dst[4] = {&p.gW1, &p.gb1, &p.gW2, &p.gb2};
     for (int i = 0; i < 4; ++i) {
       const at::Tensor& g = (*grads)[i];
       TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat && g.is_contiguous() && g.numel() == n[i],
@@ -435,71 +424,80 @@ void graph_mlp_step(at::Tensor x, at::Tensor ylab, at::Tensor W1, at::Tensor b1,
       *dst[i] = g.data_ptr<float>();
     }
   }
-  void* gp = nullptr;
-  int kind = 0;
-  if (gstep.has_value()) {
-    kind = gstep_kind_of(*gstep);
-    gp = gstep->data_ptr();
-  }
+  const GstepRef gs = gstep_ref(gstep, "graph_mlp_step");
   // L2's partials + the learning rate on the device (scratch from the caching allocator)
   at::Tensor part = at::zeros({dtfk_graph_mlp_part_floats(B, H) + 1}, x.options());
   part.narrow(0, 0, 1).fill_(lr);
-  hip_check(dtfk_graph_mlp_step(x.data_ptr<float>(), nullptr, ylab.data_ptr<float>(), W1.data_ptr<float>(),
-                                b1.data_ptr<float>(), W2.data_ptr<float>(), b2.data_ptr<float>(),
-                                a2buf.data_ptr<float>(), dz2buf.data_ptr<float>(), part.data_ptr<float>() + 1, gW1,
-                                gb1, gW2, gb2, metrics.data_ptr<float>(), nullptr, gp, kind, part.data_ptr<float>(), B, K, H, C,
-                                act, naive ? 1 : 0, sgd ? 1 : 0, cur_stream()),
-            "graph_mlp_step");
+  p.x = x.data_ptr<float>();
+  p.ylab = ylab.data_ptr<float>();
+  p.W1 = W1.data_ptr<float>();
+  p.b1 = b1.data_ptr<float>();
+  p.W2 = W2.data_ptr<float>();
+  p.b2 = b2.data_ptr<float>();
+  p.a2 = a2buf.data_ptr<float>();
+  p.dz2 = dz2buf.data_ptr<float>();
+  p.part = part.data_ptr<float>() + 1;
+  p.metrics = metrics.data_ptr<float>();
+  p.gstep = gs.ptr;
+  p.gstep_kind = gs.kind;
+  p.lr = part.data_ptr<float>();
+  p.B = B, p.K = K, p.H = H, p.C = C;
+  p.act = act, p.naive = naive ? 1 : 0, p.sgd = sgd ? 1 : 0;
+  hip_check(dtfk_graph_mlp_step(&p, cur_stream()), "graph_mlp_step");
 }
 
 // The lowered Session.run of the reference's training graph as ONE host call
 // (compat/lowering.py, in-kernel SGD): the numpy feeds x [B,K] / y_ [B,C] and the
 // learning rate go into a pinned staging slot (one memcpy, GIL released), ONE
-// host-to-device copy, then L1 / L2 / L3 and the loss / accuracy / global_step
-// device-to-host copy replayed from a captured hipGraph; with `sync` the call
-// returns after the step (the reference fetches the loss every step).
+// host-to-device copy, then L1 / L2 / L3 launched on the caller's stream (the
+// last kernel stores loss / accuracy / global_step into pinned host memory) or,
+// with `use_graph`, replayed with a metrics copy-back from a captured hipGraph
+// on the plan's own stream; with `sync` the call returns after the step (the
+// reference fetches the loss every step).
 class GraphStepPlan {
  public:
   GraphStepPlan(at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2, c10::optional<at::Tensor> gstep, int B,
                 int act, bool naive, bool use_graph)
-      : W1_(W1), b1_(b1), W2_(W2), b2_(b2), B_(B), act_(act), naive_(naive), use_graph_(use_graph) {
-    const char* df = getenv("DTF_GRAPH_STEP_DIRECT_FEED");
-    direct_feed_ = df != nullptr && df[0] == '1';
-    const char* hs = getenv("DTF_GRAPH_STEP_METRICS_COPY");   // 1: copy the metrics back with a D2H op
-    host_store_ = !(hs != nullptr && hs[0] == '1');
-    // 1: the feed read over PCIe by an ingest kernel instead of the copy engine
-    // (system-scope 8-byte loads: 17 us for the 0.3 MB feed vs ~15 us by DMA -- kept off)
-    const char* fk = getenv("DTF_GRAPH_STEP_FEED_KERNEL");
-    kernel_feed_ = fk != nullptr && fk[0] == '1';
+      : W1_(W1), b1_(b1), W2_(W2), b2_(b2), use_graph_(use_graph) {
     for (const at::Tensor* t : {&W1, &b1, &W2, &b2})
       TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
                   "GraphStepPlan: fp32 contiguous device parameters expected");
-    K_ = (int)W1.size(0);
-    H_ = (int)W1.size(1);
-    C_ = (int)W2.size(1);
-    TORCH_CHECK(W2.size(0) == H_ && b1.numel() == H_ && b2.numel() == C_, "GraphStepPlan: shape mismatch");
-    HP_ = (H_ + 16) & ~15;
-    const int BP = (B_ + 15) & ~15;
-    if (gstep.has_value()) {
-      gkind_ = gstep_kind_of(*gstep);
-      gstep_ = *gstep;
-    }
-    nfeed_ = ((int64_t)B_ * K_ + (int64_t)B_ * C_ + 1 + 3) / 4 * 4;   // x | y | lr, padded to 16 bytes
-    feed_bytes_ = nfeed_ * (int64_t)sizeof(float);
+    const int K = (int)W1.size(0), H = (int)W1.size(1), C = (int)W2.size(1);
+    TORCH_CHECK(W2.size(0) == H && b1.numel() == H && b2.numel() == C, "GraphStepPlan: shape mismatch");
+    const int HP = (H + 16) & ~15, BP = (B + 15) & ~15;
+    gs_ = gstep_ref(gstep, "GraphStepPlan");
+    if (gstep.has_value()) gstep_ = *gstep;
+    const int64_t nfeed = ((int64_t)B * K + (int64_t)B * C + 1 + 3) / 4 * 4;   // x | y | lr, padded to 16 bytes
     auto fo = W1.options();
-    dev_ = at::empty({nfeed_}, fo);
-    a2_ = at::empty({(int64_t)BP * HP_}, fo);
-    dz2_ = at::empty({(int64_t)BP * HP_}, fo);
-    part_ = at::zeros({dtfk_graph_mlp_part_floats(B_, H_)}, fo);
+    dev_ = at::empty({nfeed}, fo);
+    a2_ = at::empty({(int64_t)BP * HP}, fo);
+    dz2_ = at::empty({(int64_t)BP * HP}, fo);
+    part_ = at::zeros({dtfk_graph_mlp_part_floats(B, H)}, fo);
     metrics_ = at::zeros({4}, fo);
     auto ho = at::TensorOptions().dtype(at::kFloat).pinned_memory(true);
-    for (int i = 0; i < 2; ++i) stage_[i] = at::empty({nfeed_}, ho);
+    for (int i = 0; i < 2; ++i) stage_[i] = at::empty({nfeed}, ho);
     host_metrics_ = at::zeros({4}, ho);
     for (int i = 0; i < 2; ++i) hip_check(hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming), "hipEventCreate");
     hip_check(hipEventCreateWithFlags(&in_ev_, hipEventDisableTiming), "hipEventCreate");
     hip_check(hipEventCreateWithFlags(&out_ev_, hipEventDisableTiming), "hipEventCreate");
     // its own stream: graph capture needs one that is not the legacy default stream
     hip_check(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking), "hipStreamCreate");
+    // everything of the step but the feed pointers (launch_step sets them per launch)
+    step_.W1 = W1.data_ptr<float>();
+    step_.b1 = b1.data_ptr<float>();
+    step_.W2 = W2.data_ptr<float>();
+    step_.b2 = b2.data_ptr<float>();
+    step_.a2 = a2_.data_ptr<float>();
+    step_.dz2 = dz2_.data_ptr<float>();
+    step_.part = part_.data_ptr<float>();
+    step_.metrics = metrics_.data_ptr<float>();
+    // direct launches: the last kernel stores the metrics into the pinned buffer;
+    // a captured graph copies them back instead
+    step_.host_metrics = use_graph_ ? nullptr : host_metrics_.data_ptr<float>();
+    step_.gstep = gs_.ptr;
+    step_.gstep_kind = gs_.kind;
+    step_.B = B, step_.K = K, step_.H = H, step_.C = C;
+    step_.act = act, step_.naive = naive ? 1 : 0, step_.sgd = 1;
   }
   ~GraphStepPlan() {
     if (exec_) (void)hipGraphExecDestroy(exec_);
@@ -524,8 +522,16 @@ class GraphStepPlan {
     TORCH_CHECK(!use_graph_, "GraphStepPlan.attach_ipc: direct-launch plans only");
     ipc_obj_ = coll;
     ipc_ = coll.cast<IpcColl*>();
-    const int64_t n = (int64_t)K_ * H_ + H_ + (int64_t)H_ * C_ + C_;
-    grad_ = at::zeros({(n + 1) & ~1LL}, W1_.options());
+    const int64_t nW1 = (int64_t)step_.K * step_.H, nW2 = (int64_t)step_.H * step_.C;
+    grad_ = at::zeros({(nW1 + step_.H + nW2 + step_.C + 1) & ~1LL}, W1_.options());
+    // gradients out (flat, variable order); the reduce + SGD kernel bumps global_step
+    step_.gW1 = grad_.data_ptr<float>();
+    step_.gb1 = step_.gW1 + nW1;
+    step_.gW2 = step_.gb1 + step_.H;
+    step_.gb2 = step_.gW2 + nW2;
+    step_.sgd = 0;
+    step_.gstep = nullptr;
+    step_.gstep_kind = dtfk::GSTEP_NONE;
   }
   bool has_ipc() const { return ipc_ != nullptr; }
 
@@ -533,134 +539,31 @@ class GraphStepPlan {
   // shapes.  Returns after the step when `sync` (host_metrics() then holds
   // loss, accuracy, global_step after the step).
   void run(py::array x, py::array y, double lr, bool sync) {
-    const int64_t nx = (int64_t)B_ * K_, ny = (int64_t)B_ * C_;
     TORCH_CHECK(x.dtype().is(py::dtype::of<float>()) && y.dtype().is(py::dtype::of<float>()),
                 "GraphStepPlan.run: float32 feeds expected");
     TORCH_CHECK((x.flags() & py::array::c_style) && (y.flags() & py::array::c_style),
                 "GraphStepPlan.run: C-contiguous feeds expected");
-    TORCH_CHECK(x.size() == nx && y.size() == ny, "GraphStepPlan.run: feed shapes differ from the plan's");
-    const float* xp = static_cast<const float*>(x.data());
-    const float* yp = static_cast<const float*>(y.data());
-    hipStream_t cur = cur_stream(), st = use_graph_ ? st_ : cur;
-    const int slot = slot_ ^= 1;
-    {
-      py::gil_scoped_release nogil;
-      if (!use_graph_) {   // direct launches on the caller's stream: no cross-stream events, no replay floor
-        using clk = std::chrono::steady_clock;
-        const auto t0 = clk::now();
-        // the copy that last read this staging slot: only an unsynchronized call
-        // leaves one in flight (a synchronizing call needs no event at all)
-        if (pending_[slot]) hip_check(hipEventSynchronize(ev_[slot]), "GraphStepPlan: staging slot");
-        pending_[slot] = false;
-        float* h = stage_[slot].data_ptr<float>();
-        float* d = dev_.data_ptr<float>();
-        if (direct_feed_) {
-          // x / y_ straight from the caller's memory (zero-copy DMA when it is
-          // pinned; HIP's own pipelined staging when pageable); lr via the slot
-          h[nx + ny] = (float)lr;
-          hip_check(hipMemcpyAsync(d, xp, sizeof(float) * nx, hipMemcpyHostToDevice, st), "GraphStepPlan: x copy");
-          hip_check(hipMemcpyAsync(d + nx, yp, sizeof(float) * ny, hipMemcpyHostToDevice, st), "GraphStepPlan: y copy");
-          hip_check(hipMemcpyAsync(d + nx + ny, h + nx + ny, sizeof(float), hipMemcpyHostToDevice, st),
-                    "GraphStepPlan: lr copy");
-        } else {
-          std::memcpy(h, xp, sizeof(float) * nx);
-          std::memcpy(h + nx, yp, sizeof(float) * ny);
-          h[nx + ny] = (float)lr;
-          t_[0] += std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-          if (kernel_feed_)   // workgroups read the pinned slot over PCIe (no copy-engine op)
-            hip_check(dtfk_graph_feed_ingest(h, d, feed_bytes_, st), "GraphStepPlan: feed ingest");
-          else
-            hip_check(hipMemcpyAsync(d, h, sizeof(float) * (nx + ny + 1), hipMemcpyHostToDevice, st),
-                      "GraphStepPlan: feed copy");
-        }
-        if (!sync) {
-          hip_check(hipEventRecord(ev_[slot], st), "GraphStepPlan: event");
-          pending_[slot] = true;
-        }
-        hip_check(launch_step(st, host_store_), "GraphStepPlan: launch");
-        const auto t2 = clk::now();
-        t_[1] += std::chrono::duration<double, std::micro>(t2 - t0).count();
-        if (sync) {
-          hip_check(hipStreamSynchronize(st), "GraphStepPlan: sync");
-          pending_[0] = pending_[1] = false;
-        }
-        t_[2] += std::chrono::duration<double, std::micro>(clk::now() - t2).count();
-        ++steps_;
-        return;
-      }
-      hip_check(hipEventSynchronize(ev_[slot]), "GraphStepPlan: staging slot");   // its last copy is done
-      pending_[slot] = false;
-      float* h = stage_[slot].data_ptr<float>();
-      std::memcpy(h, xp, sizeof(float) * nx);
-      std::memcpy(h + nx, yp, sizeof(float) * ny);
-      h[nx + ny] = (float)lr;
-      // after whatever the caller's stream queued (variable init, eager updates)
-      hip_check(hipEventRecord(in_ev_, cur), "GraphStepPlan: event");
-      hip_check(hipStreamWaitEvent(st, in_ev_, 0), "GraphStepPlan: wait");
-      hip_check(hipMemcpyAsync(dev_.data_ptr<float>(), h, sizeof(float) * (nx + ny + 1), hipMemcpyHostToDevice, st),
-                "GraphStepPlan: feed copy");
-      hip_check(hipEventRecord(ev_[slot], st), "GraphStepPlan: event");
-      if (exec_ == nullptr) capture(st);
-      hip_check(hipGraphLaunch(exec_, st), "GraphStepPlan: graph launch");
-      if (sync) {
-        hip_check(hipStreamSynchronize(st), "GraphStepPlan: sync");
-      } else {   // later work on the caller's stream sees the updated variables
-        hip_check(hipEventRecord(out_ev_, st), "GraphStepPlan: event");
-        hip_check(hipStreamWaitEvent(cur, out_ev_, 0), "GraphStepPlan: wait");
-      }
-    }
-    ++steps_;
+    TORCH_CHECK(x.size() == nx() && y.size() == ny(), "GraphStepPlan.run: feed shapes differ from the plan's");
+    step(x.data(), static_cast<const float*>(y.data()), lr, false, sync);
   }
   // The same step fed uint8 pixels (the MNIST loader's source bytes of a float
   // batch x = u8 / 255, data/mnist.py): a 4x smaller staging copy and transfer;
   // the kernels convert with the loader's exact float32 division, so the step is
   // bit-identical to run() with that float batch.  Direct launches only.
   void run_u8(py::array xu8, py::array y, double lr, bool sync) {
-    const int64_t nx = (int64_t)B_ * K_, ny = (int64_t)B_ * C_;
     TORCH_CHECK(!use_graph_, "GraphStepPlan.run_u8: direct-launch plans only");
     TORCH_CHECK(xu8.dtype().is(py::dtype::of<uint8_t>()) && y.dtype().is(py::dtype::of<float>()),
                 "GraphStepPlan.run_u8: uint8 x and float32 y_ expected");
     TORCH_CHECK((xu8.flags() & py::array::c_style) && (y.flags() & py::array::c_style),
                 "GraphStepPlan.run_u8: C-contiguous feeds expected");
-    TORCH_CHECK(xu8.size() == nx && y.size() == ny, "GraphStepPlan.run_u8: feed shapes differ from the plan's");
-    TORCH_CHECK(K_ % 4 == 0, "GraphStepPlan.run_u8: K % 4 == 0 expected");
-    const uint8_t* xp = static_cast<const uint8_t*>(xu8.data());
-    const float* yp = static_cast<const float*>(y.data());
-    hipStream_t st = cur_stream();
-    const int slot = slot_ ^= 1;
-    const int64_t xf = u8_x_floats();
-    {
-      py::gil_scoped_release nogil;
-      using clk = std::chrono::steady_clock;
-      const auto t0 = clk::now();
-      if (pending_[slot]) hip_check(hipEventSynchronize(ev_[slot]), "GraphStepPlan: staging slot");
-      pending_[slot] = false;
-      float* h = stage_[slot].data_ptr<float>();
-      std::memcpy(h, xp, (size_t)nx);
-      std::memcpy(h + xf, yp, sizeof(float) * ny);
-      h[xf + ny] = (float)lr;
-      t_[0] += std::chrono::duration<double, std::micro>(clk::now() - t0).count();
-      hip_check(hipMemcpyAsync(dev_.data_ptr<float>(), h, sizeof(float) * (xf + ny + 1), hipMemcpyHostToDevice, st),
-                "GraphStepPlan: feed copy");
-      if (!sync) {
-        hip_check(hipEventRecord(ev_[slot], st), "GraphStepPlan: event");
-        pending_[slot] = true;
-      }
-      hip_check(launch_step(st, host_store_, true), "GraphStepPlan: launch");
-      const auto t2 = clk::now();
-      t_[1] += std::chrono::duration<double, std::micro>(t2 - t0).count();
-      if (sync) {
-        hip_check(hipStreamSynchronize(st), "GraphStepPlan: sync");
-        pending_[0] = pending_[1] = false;
-      }
-      t_[2] += std::chrono::duration<double, std::micro>(clk::now() - t2).count();
-      ++steps_;
-    }
+    TORCH_CHECK(xu8.size() == nx() && y.size() == ny(), "GraphStepPlan.run_u8: feed shapes differ from the plan's");
+    TORCH_CHECK(step_.K % 4 == 0, "GraphStepPlan.run_u8: K % 4 == 0 expected");
+    step(xu8.data(), static_cast<const float*>(y.data()), lr, true, sync);
   }
   int64_t steps() const { return steps_; }
   bool use_graph() const { return use_graph_; }
-  // host-side split of the direct-launch calls so far, us per call: feed copy
-  // into the staging slot, everything up to the last enqueue, the final wait
+  // host-side split of the calls so far, us per call: feed copy into the
+  // staging slot, everything up to the last enqueue, the final wait
   py::dict timing() const {
     py::dict d;
     const double n = steps_ > 0 ? (double)steps_ : 1.0;
@@ -672,47 +575,86 @@ class GraphStepPlan {
   }
 
  private:
-  // the step's three kernels on stream st; the metrics reach host_metrics_
-  // either from the last kernel itself (system-scope stores into the pinned
-  // buffer: direct launches) or by a copy back (captured graphs)
-  hipError_t launch_step(hipStream_t st, bool host_store, bool u8 = false) {
-    const int64_t nx = (int64_t)B_ * K_, ny = (int64_t)B_ * C_;
-    float* d = dev_.data_ptr<float>();
-    // uint8 feed: [x bytes padded to 16 | y_ | lr] in the same device buffer
-    const uint8_t* xu = u8 ? reinterpret_cast<const uint8_t*>(d) : nullptr;
-    float* yd = u8 ? d + u8_x_floats() : d + nx;
-    float* gW1 = nullptr, *gb1 = nullptr, *gW2 = nullptr, *gb2 = nullptr;
-    if (ipc_ != nullptr) {     // gradients out (flat, variable order), then the IPC reduce + SGD
-      gW1 = grad_.data_ptr<float>();
-      gb1 = gW1 + (int64_t)K_ * H_;
-      gW2 = gb1 + H_;
-      gb2 = gW2 + (int64_t)H_ * C_;
+  int64_t nx() const { return (int64_t)step_.B * step_.K; }
+  int64_t ny() const { return (int64_t)step_.B * step_.C; }
+  // floats x occupies at the front of the feed buffer: [x | y_ | lr], uint8 x padded to 16 bytes
+  int64_t x_floats(bool u8) const { return u8 ? (nx() + 15) / 16 * 4 : nx(); }
+
+  // The one run path.  xp: nx() floats, or bytes when `u8`.  Take the other
+  // staging slot (waiting for the copy an unsynchronized call left in flight on
+  // it), pack x | y_ | lr into it, ONE host-to-device copy, the step.  Direct
+  // launches go on the caller's stream: no cross-stream events, no replay floor.
+  // A captured plan runs on its own stream, after whatever the caller's stream
+  // queued (variable init, eager updates) and, when not syncing, before what it
+  // queues next.
+  void step(const void* xp, const float* yp, double lr, bool u8, bool sync) {
+    using clk = std::chrono::steady_clock;
+    const int64_t xf = x_floats(u8), nyf = ny();
+    hipStream_t cur = cur_stream(), st = use_graph_ ? st_ : cur;
+    const int slot = slot_ ^= 1;
+    py::gil_scoped_release nogil;
+    const auto t0 = clk::now();
+    if (pending_[slot]) hip_check(hipEventSynchronize(ev_[slot]), "GraphStepPlan: staging slot");
+    pending_[slot] = false;
+    float* h = stage_[slot].data_ptr<float>();
+    std::memcpy(h, xp, u8 ? (size_t)nx() : sizeof(float) * nx());
+    std::memcpy(h + xf, yp, sizeof(float) * nyf);
+    h[xf + nyf] = (float)lr;
+    t_[0] += std::chrono::duration<double, std::micro>(clk::now() - t0).count();
+    if (use_graph_) {
+      hip_check(hipEventRecord(in_ev_, cur), "GraphStepPlan: event");
+      hip_check(hipStreamWaitEvent(st, in_ev_, 0), "GraphStepPlan: wait");
     }
-    hipError_t e = dtfk_graph_mlp_step(u8 ? nullptr : d, xu, yd, W1_.data_ptr<float>(), b1_.data_ptr<float>(), W2_.data_ptr<float>(),
-                                       b2_.data_ptr<float>(), a2_.data_ptr<float>(), dz2_.data_ptr<float>(),
-                                       part_.data_ptr<float>(), gW1, gb1, gW2, gb2,
-                                       metrics_.data_ptr<float>(), host_store ? host_metrics_.data_ptr<float>() : nullptr,
-                                       ipc_ == nullptr && gstep_.defined() ? gstep_.data_ptr() : nullptr, gkind_,
-                                       yd + ny, B_, K_, H_, C_, act_, naive_ ? 1 : 0, ipc_ == nullptr ? 1 : 0, st);
-    if (e == hipSuccess && ipc_ != nullptr) {
-      {   // (throws on a failed earlier collective; chains streams like every IPC call)
-        (void)ipc_->begin();
-        ipc_->reduce_sgd_raw(grad_.data_ptr<float>(), (int64_t)K_ * H_ + H_ + (int64_t)H_ * C_ + C_,
-                             {W1_.data_ptr<float>(), b1_.data_ptr<float>(), W2_.data_ptr<float>(), b2_.data_ptr<float>()},
-                             {(int64_t)K_ * H_, (int64_t)H_, (int64_t)H_ * C_, (int64_t)C_}, yd + ny, 0.f,
-                             1.f / (float)ipc_->world_size(), gstep_.defined() ? gstep_.data_ptr() : nullptr, gkind_,
-                             metrics_.data_ptr<float>(), host_store ? host_metrics_.data_ptr<float>() : nullptr, st);
+    hip_check(hipMemcpyAsync(dev_.data_ptr<float>(), h, sizeof(float) * (xf + nyf + 1), hipMemcpyHostToDevice, st),
+              "GraphStepPlan: feed copy");
+    if (!sync) {   // a synchronizing call leaves no copy in flight: no event at all
+      hip_check(hipEventRecord(ev_[slot], st), "GraphStepPlan: event");
+      pending_[slot] = true;
+    }
+    if (use_graph_) {
+      if (exec_ == nullptr) capture(st);
+      hip_check(hipGraphLaunch(exec_, st), "GraphStepPlan: graph launch");
+      if (!sync) {   // later work on the caller's stream sees the updated variables
+        hip_check(hipEventRecord(out_ev_, st), "GraphStepPlan: event");
+        hip_check(hipStreamWaitEvent(cur, out_ev_, 0), "GraphStepPlan: wait");
       }
+    } else {
+      hip_check(launch_step(st, u8), "GraphStepPlan: launch");
     }
-    if (e == hipSuccess && !host_store)
-      e = hipMemcpyAsync(host_metrics_.data_ptr<float>(), metrics_.data_ptr<float>(), 3 * sizeof(float),
-                         hipMemcpyDeviceToHost, st);
+    const auto t2 = clk::now();
+    t_[1] += std::chrono::duration<double, std::micro>(t2 - t0).count();
+    if (sync) {
+      hip_check(hipStreamSynchronize(st), "GraphStepPlan: sync");
+      pending_[0] = pending_[1] = false;
+    }
+    t_[2] += std::chrono::duration<double, std::micro>(clk::now() - t2).count();
+    ++steps_;
+  }
+
+  // the step's kernels on stream st, fed from dev_; with IPC the reduce + SGD
+  // kernel follows; a captured graph ends with the metrics copy-back
+  hipError_t launch_step(hipStream_t st, bool u8) {
+    float* d = dev_.data_ptr<float>();
+    step_.x = u8 ? nullptr : d;
+    step_.xu = u8 ? reinterpret_cast<const uint8_t*>(d) : nullptr;
+    step_.ylab = d + x_floats(u8);
+    step_.lr = step_.ylab + ny();
+    hipError_t e = dtfk_graph_mlp_step(&step_, st);
+    if (e == hipSuccess && ipc_ != nullptr) {
+      (void)ipc_->begin();   // (throws on a failed earlier collective; chains streams like every IPC call)
+      const int64_t nW1 = (int64_t)step_.K * step_.H, nW2 = (int64_t)step_.H * step_.C;
+      ipc_->reduce_sgd_raw(grad_.data_ptr<float>(), nW1 + step_.H + nW2 + step_.C,
+                           {step_.W1, step_.b1, step_.W2, step_.b2}, {nW1, (int64_t)step_.H, nW2, (int64_t)step_.C},
+                           step_.lr, 0.f, 1.f / (float)ipc_->world_size(), gs_.ptr, gs_.kind, step_.metrics,
+                           step_.host_metrics, st);
+    }
+    if (e == hipSuccess && use_graph_)
+      e = hipMemcpyAsync(host_metrics_.data_ptr<float>(), step_.metrics, 3 * sizeof(float), hipMemcpyDeviceToHost, st);
     return e;
   }
 
   void capture(hipStream_t st) {
-    if (exec_) { (void)hipGraphExecDestroy(exec_); exec_ = nullptr; }
-    if (graph_) { (void)hipGraphDestroy(graph_); graph_ = nullptr; }
+    if (graph_) { (void)hipGraphDestroy(graph_); graph_ = nullptr; }   // left by a failed instantiate
     hip_check(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal), "GraphStepPlan: begin capture");
     const hipError_t e = launch_step(st, false);
     hipGraph_t g = nullptr;
@@ -723,9 +665,6 @@ class GraphStepPlan {
     hip_check(hipGraphInstantiate(&exec_, graph_, nullptr, nullptr, 0), "GraphStepPlan: instantiate");
   }
 
-  // floats the uint8 x occupies at the front of the feed buffer (16-byte padded)
-  int64_t u8_x_floats() const { return ((int64_t)B_ * K_ + 15) / 16 * 4; }
-
   at::Tensor W1_, b1_, W2_, b2_, gstep_, dev_, a2_, dz2_, part_, metrics_, host_metrics_, grad_;
   at::Tensor stage_[2];
   py::object ipc_obj_;
@@ -735,12 +674,12 @@ class GraphStepPlan {
   hipGraph_t graph_ = nullptr;
   hipGraphExec_t exec_ = nullptr;
   hipStream_t st_ = nullptr;
-  int B_, K_ = 0, H_ = 0, C_ = 0, HP_ = 0, act_, gkind_ = 0, slot_ = 0;
-  bool naive_, use_graph_, direct_feed_ = false;
-  int64_t nfeed_ = 0, steps_ = 0;
-  bool host_store_ = true, kernel_feed_ = false;
+  dtfk::gmlp::Step step_{};   // filled at construction / attach_ipc; launch_step sets the feed pointers
+  GstepRef gs_;               // the graph's global_step (with IPC the reduce + SGD kernel bumps it)
+  bool use_graph_;
+  int slot_ = 0;
+  int64_t steps_ = 0;
   bool pending_[2] = {false, false};   // an event on the staging slot's copy may still be in flight
-  int64_t feed_bytes_ = 0;
   double t_[3] = {0, 0, 0};
 };
 
@@ -768,11 +707,8 @@ class ResidentMLPPlan {
                 "ResidentMLPPlan: the reference's 784-100-10 shapes expected");
     TORCH_CHECK(B >= 1 && B <= dtfk_mlpf_max_batch(), "ResidentMLPPlan: batch must be in [1, ",
                 dtfk_mlpf_max_batch(), "]");
-    if (gstep.has_value()) {
-      const int k = gstep_kind_of(*gstep);   // 0 f32, 1 i64, 2 i32, 3 f64
-      gkind_ = k + 1;
-      gstep_ = *gstep;
-    }
+    gkind_ = gstep_ref(gstep, "ResidentMLPPlan").kind;
+    if (gstep.has_value()) gstep_ = *gstep;
     rec_h_ = ((int64_t)B * 785 + 15) / 16 * 16;
     const size_t bytes = 512 + 2 * (size_t)rec_h_;
     hip_check(hipHostMalloc(&mail_, bytes, hipHostMallocMapped | hipHostMallocCoherent), "ResidentMLPPlan: mailbox");

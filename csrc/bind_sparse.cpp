@@ -17,6 +17,8 @@
 #include <pybind11/numpy.h>
 #include <hip/hip_runtime.h>
 
+#include "gstep_host.h"
+
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -53,18 +55,8 @@ class SparseLRPlan {
     TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat && bias.numel() == 1 && bias.is_contiguous(),
                 "SparseLRPlan: bias must be one fp32 GPU value");
     F_ = W.size(0);
-    if (gstep.has_value()) {
-      const at::Tensor& g = *gstep;
-      TORCH_CHECK(g.is_cuda() && g.numel() == 1, "SparseLRPlan: device scalar global_step");
-      switch (g.scalar_type()) {
-        case at::kFloat: gkind_ = 1; break;
-        case at::kLong: gkind_ = 2; break;
-        case at::kInt: gkind_ = 3; break;
-        case at::kDouble: gkind_ = 4; break;
-        default: TORCH_CHECK(false, "SparseLRPlan: unsupported global_step dtype");
-      }
-      gstep_ = g;
-    }
+    gs_ = gstep_ref(gstep, "SparseLRPlan");
+    if (gstep.has_value()) gstep_ = *gstep;   // keeps gs_.ptr alive
     auto fo = W.options();
     loss_ = at::zeros({1}, fo);
     bad_ = at::zeros({1}, fo.dtype(at::kInt));
@@ -284,7 +276,7 @@ class SparseLRPlan {
                                    d + o_ids, reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
                                    bias_.data_ptr<float>(), (int)B, (float)lr, dz_.data_ptr<float>(),
                                    lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
-                                   gkind_ ? gstep_.data_ptr() : nullptr, gkind_, st),
+                                   gs_.ptr, gs_.kind, st),
               "SparseLRPlan: step");
           hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
           pending_[slot] = true;
@@ -360,7 +352,7 @@ class SparseLRPlan {
               float lr, hipStream_t st) {
     hck(dtfk_slr_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, bias_.data_ptr<float>(), B, nullptr,
                       lr, dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(),
-                      bad_.data_ptr<int>(), gkind_ ? gstep_.data_ptr() : nullptr, gkind_, st),
+                      bad_.data_ptr<int>(), gs_.ptr, gs_.kind, st),
         "SparseLRPlan: step");
   }
 
@@ -375,7 +367,8 @@ class SparseLRPlan {
   std::vector<int64_t> cnt_;
   hipEvent_t ev_[2] = {nullptr, nullptr};
   bool pending_[2] = {false, false};
-  int slot_ = 0, gkind_ = 0;
+  GstepRef gs_;
+  int slot_ = 0;
   int64_t F_ = 0, runs_ = 0;
   double t_[3] = {0, 0, 0};
 };

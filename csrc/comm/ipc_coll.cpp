@@ -4,6 +4,7 @@
 // csrc/kernels/ipc_coll.hip).  parallel/world.py routes World's GPU
 // collectives here.
 #include "comm/ipc_coll_host.h"
+#include "gstep_host.h"
 
 namespace dtf {
 namespace {
@@ -101,19 +102,7 @@ void reduce_sgd(IpcColl& c, at::Tensor grad, std::vector<at::Tensor> params, c10
     n += p.numel();
   }
   if (grad.numel() < n) throw std::runtime_error("IpcColl.reduce_sgd: gradient smaller than the parameters");
-  void* gs = nullptr;
-  int gk = 0;
-  if (gstep.has_value()) {
-    need_cuda_contig(*gstep, "IpcColl.reduce_sgd global_step");
-    switch (gstep->scalar_type()) {
-      case at::kFloat: gk = 0; break;
-      case at::kLong: gk = 1; break;
-      case at::kInt: gk = 2; break;
-      case at::kDouble: gk = 3; break;
-      default: throw std::runtime_error("IpcColl.reduce_sgd: global_step dtype");
-    }
-    gs = gstep->data_ptr();
-  }
+  const GstepRef gs = gstep_ref(gstep, "IpcColl.reduce_sgd");
   const float* lp = nullptr;
   if (lr.has_value()) {
     need_cuda_contig(*lr, "IpcColl.reduce_sgd lr");
@@ -121,8 +110,8 @@ void reduce_sgd(IpcColl& c, at::Tensor grad, std::vector<at::Tensor> params, c10
   }
   float* hm = host_metrics.has_value() ? host_metrics->data_ptr<float>() : nullptr;
   hipStream_t s = c.begin();
-  c.reduce_sgd_raw(grad.data_ptr<float>(), n, ps, ns, lp, (float)lr_val, 1.f / (float)c.world_size(), gs, gk, nullptr,
-                   hm, s);
+  c.reduce_sgd_raw(grad.data_ptr<float>(), n, ps, ns, lp, (float)lr_val, 1.f / (float)c.world_size(), gs.ptr, gs.kind,
+                   nullptr, hm, s);
 }
 
 }  // namespace

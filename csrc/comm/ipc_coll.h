@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gstep_kind.h"
+
 namespace dtfk {
 namespace ipcc {
 
@@ -39,7 +41,7 @@ struct SgdArgs {                 // fused all-reduce-mean + SGD over up to 8 fp3
   float lr_val;
   float scale;                   // 1 / W (mean)
   void* gstep;                   // global_step storage (+1 once per step) or null
-  int gkind;                     // 0 f32, 1 i64, 2 i32, 3 f64
+  int gkind;                     // gstep_kind.h (GSTEP_NONE with a null gstep)
   float* metrics;                // [2] <- global_step after the update (or null)
   float* host_metrics;           // pinned [2] <- the same (or null)
 };

@@ -30,10 +30,11 @@
 // tile, x's virtual column K gives db1 in L3), so no serial column sums.
 // Shapes: any B <= 256 with B*HP <= 16384 (HP = H + 1 rounded up to 16),
 // K >= 1, H <= 128, C <= 16.
+// Rejected: an ingest kernel reading the pinned feed slot over PCIe instead of the
+// copy-engine transfer (17 us for the 0.3 MB feed vs ~15 us by DMA); removed.
 #include "common.h"
+#include "gstep_kind.h"
 #include "mlp_api.h"
-
-#include <algorithm>
 
 namespace dtfk {
 namespace gmlp {
@@ -341,7 +342,7 @@ struct WgradArgs {
   float* metrics;       // [0] loss, [1] accuracy, [2] global_step after the step
   float* host_metrics;  // the same three in pinned host memory (nullptr: none) -- no copy-back op
   void* gstep;          // global_step storage or nullptr
-  int gstep_kind;       // 0 f32, 1 i64, 2 i32, 3 f64
+  int gstep_kind;       // gstep_kind.h
   const float* lr_ptr;  // device learning rate (a captured step reads the current one)
   int B, K, H, HP, C, sgd, tiles;
 };
@@ -376,9 +377,9 @@ __device__ void graph_mlp_w2_final(const WgradArgs& a, int ht) {
     if (a.gstep != nullptr) {
       float now;
       switch (a.gstep_kind) {
-        case 0: now = (*reinterpret_cast<float*>(a.gstep) += 1.f); break;
-        case 1: now = (float)(*reinterpret_cast<long long*>(a.gstep) += 1); break;
-        case 2: now = (float)(*reinterpret_cast<int*>(a.gstep) += 1); break;
+        case GSTEP_F32: now = (*reinterpret_cast<float*>(a.gstep) += 1.f); break;
+        case GSTEP_I64: now = (float)(*reinterpret_cast<long long*>(a.gstep) += 1); break;
+        case GSTEP_I32: now = (float)(*reinterpret_cast<int*>(a.gstep) += 1); break;
         default: now = (float)(*reinterpret_cast<double*>(a.gstep) += 1.0); break;
       }
       a.metrics[2] = now;                 // post-increment value, read back with the loss
@@ -455,33 +456,8 @@ __global__ __launch_bounds__(256) void graph_mlp_wgrad(WgradArgs a) {
   }
 }
 
-// Feed ingest: the step's packed feed (x | y_ | lr) read straight from the
-// pinned host staging slot over PCIe by many workgroups (16-byte loads), instead
-// of a copy-engine transfer -- for a ~0.3 MB feed the DMA's setup / completion
-// latency is most of its time.  n4: 16-byte chunks (the tail pads to a chunk).
-// The slot is rewritten by the host every other step: system-scope loads (no
-// stale cached copy of the previous use).
-__global__ __launch_bounds__(256) void feed_ingest(const uint4* __restrict__ host, uint4* __restrict__ dev,
-                                                   long long n4) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long lo = ld_sys_u64(host + i), hi = ld_sys_u64(reinterpret_cast<const char*>(host + i) + 8);
-    dev[i] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
-  }
-}
-
 }  // namespace gmlp
 }  // namespace dtfk
-
-extern "C" hipError_t dtfk_graph_feed_ingest(const void* host, void* dev, long long bytes, hipStream_t stream) {
-  if (bytes <= 0) return hipSuccess;
-  if ((reinterpret_cast<uintptr_t>(host) | reinterpret_cast<uintptr_t>(dev) | (uintptr_t)bytes) & 15)
-    return hipErrorInvalidValue;
-  const long long n4 = bytes / 16;
-  const unsigned grid = (unsigned)std::min<long long>(160, (n4 + 255) / 256);
-  hipLaunchKernelGGL(dtfk::gmlp::feed_ingest, dim3(grid), dim3(256), 0, stream, static_cast<const uint4*>(host),
-                     static_cast<uint4*>(dev), n4);
-  return hipGetLastError();
-}
 
 // Device scratch (floats) the step needs besides a2 / dz2: L2's partials + loss
 // sums + the per-row-tile arrival counters (int).  Must be ZERO when first used.
@@ -490,33 +466,31 @@ extern "C" long long dtfk_graph_mlp_part_floats(int B, int H) {
   return (long long)NRT * HP * dtfk::gmlp::CP + 3LL * NRT;
 }
 
-// xu (uint8 pixels, K % 4 == 0, 4-byte aligned) replaces x when non-null.
-extern "C" hipError_t dtfk_graph_mlp_step(const float* x, const uint8_t* xu, const float* ylab, float* W1, float* b1,
-                                          float* W2,
-                                          float* b2, float* a2buf, float* dz2buf, float* part, float* gW1, float* gb1,
-                                          float* gW2, float* gb2, float* metrics, float* host_metrics, void* gstep,
-                                          int gstep_kind, const float* lr_ptr, int B, int K, int H, int C, int act,
-                                          int naive, int sgd, hipStream_t stream) {
+extern "C" hipError_t dtfk_graph_mlp_step(const dtfk::gmlp::Step* p, hipStream_t stream) {
   using namespace dtfk::gmlp;
-  if (B < 1 || B > MAXB || H < 1 || H > MAXH || C < 1 || C > CP || K < 1 || lr_ptr == nullptr)
+  const int B = p->B, K = p->K, H = p->H, C = p->C;
+  if (B < 1 || B > MAXB || H < 1 || H > MAXH || C < 1 || C > CP || K < 1 || p->lr == nullptr)
     return hipErrorInvalidValue;
   const int HP = (H + 16) & ~15, BP = (B + 15) & ~15;   // >= H + 1 (ones column)
   if (BP * HP > A2_LDS) return hipErrorInvalidValue;
-  if (xu != nullptr && ((K & 3) || (reinterpret_cast<uintptr_t>(xu) & 3))) return hipErrorInvalidValue;
-  const bool vec = (K & 3) == 0 && K >= 4 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  HeadArgs h{a2buf, ylab, W2, b2, dz2buf, part, B, H, HP, C, act, naive};
+  if (p->xu != nullptr && ((K & 3) || (reinterpret_cast<uintptr_t>(p->xu) & 3))) return hipErrorInvalidValue;
+  if (p->gstep_kind < dtfk::GSTEP_NONE || p->gstep_kind > dtfk::GSTEP_F64 ||
+      (p->gstep_kind != dtfk::GSTEP_NONE) != (p->gstep != nullptr))
+    return hipErrorInvalidValue;
+  const bool vec = (K & 3) == 0 && K >= 4 && (reinterpret_cast<uintptr_t>(p->x) & 15) == 0;
+  HeadArgs h{p->a2, p->ylab, p->W2, p->b2, p->dz2, p->part, B, H, HP, C, p->act, p->naive};
   // per-row-tile arrival counters behind the partials (zero at allocation, reset by their last arriver)
-  int* cnt = reinterpret_cast<int*>(part + (size_t)(BP / 16) * HP * CP + 2 * (BP / 16));
+  int* cnt = reinterpret_cast<int*>(p->part + (size_t)(BP / 16) * HP * CP + 2 * (BP / 16));
   const dim3 g1((BP / 16) * (HP / 16));
-  if (xu != nullptr)
-    hipLaunchKernelGGL((graph_mlp_l1h<true, true>), g1, dim3(512), 0, stream, x, xu, W1, b1, h, K, cnt);
+  if (p->xu != nullptr)
+    hipLaunchKernelGGL((graph_mlp_l1h<true, true>), g1, dim3(512), 0, stream, p->x, p->xu, p->W1, p->b1, h, K, cnt);
   else if (vec)
-    hipLaunchKernelGGL((graph_mlp_l1h<true, false>), g1, dim3(512), 0, stream, x, xu, W1, b1, h, K, cnt);
+    hipLaunchKernelGGL((graph_mlp_l1h<true, false>), g1, dim3(512), 0, stream, p->x, p->xu, p->W1, p->b1, h, K, cnt);
   else
-    hipLaunchKernelGGL((graph_mlp_l1h<false, false>), g1, dim3(512), 0, stream, x, xu, W1, b1, h, K, cnt);
+    hipLaunchKernelGGL((graph_mlp_l1h<false, false>), g1, dim3(512), 0, stream, p->x, p->xu, p->W1, p->b1, h, K, cnt);
   const int tiles = ((K + 1 + 15) / 16) * (HP / 16);
-  WgradArgs wa{x, xu, dz2buf, W1, b1, W2, b2, gW1, gb1, gW2, gb2, part, metrics, host_metrics, gstep, gstep_kind,
-               lr_ptr, B, K, H, HP, C, sgd, tiles};
+  WgradArgs wa{p->x, p->xu, p->dz2, p->W1, p->b1, p->W2, p->b2, p->gW1, p->gb1, p->gW2, p->gb2, p->part, p->metrics,
+               p->host_metrics, p->gstep, p->gstep_kind, p->lr, B, K, H, HP, C, p->sgd, tiles};
   hipLaunchKernelGGL(graph_mlp_wgrad, dim3(tiles + HP / 16), dim3(256), 0, stream, wa);
   return hipGetLastError();
 }

@@ -353,9 +353,9 @@ __global__ __launch_bounds__(256) void reduce_sgd_k(const float* __restrict__ gr
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.gstep != nullptr) {
     float now;
     switch (a.gkind) {
-      case 0: now = (*static_cast<float*>(a.gstep) += 1.f); break;
-      case 1: now = (float)(*static_cast<long long*>(a.gstep) += 1); break;
-      case 2: now = (float)(*static_cast<int*>(a.gstep) += 1); break;
+      case GSTEP_F32: now = (*static_cast<float*>(a.gstep) += 1.f); break;
+      case GSTEP_I64: now = (float)(*static_cast<long long*>(a.gstep) += 1); break;
+      case GSTEP_I32: now = (float)(*static_cast<int*>(a.gstep) += 1); break;
       default: now = (float)(*static_cast<double*>(a.gstep) += 1.0); break;
     }
     if (a.metrics != nullptr) a.metrics[2] = now;

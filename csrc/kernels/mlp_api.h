@@ -49,13 +49,45 @@ struct Launch {
   long long* host_done;
   long long* host_state;
   long long launch_id, run0, idle;
-  void* gvar;               // the graph's global_step variable (kind 0 none, 1 f32, 2 i64, 3 i32, 4 f64)
+  void* gvar;               // the graph's global_step variable and its dtype code (csrc/gstep_kind.h)
   int gvar_kind;
   unsigned* dctr;
   long long* res_ts;        // profiling: [64][8] per-run stamps -> the instrumented resident build
 };
 
 }  // namespace mlpf
+
+namespace gmlp {
+
+// One step of the compat Session's lowered MLP graph (graph_mlp.hip).  Value-
+// initialise it (`Step p{}`) and set what the mode needs; everything else
+// stays null / zero.
+struct Step {
+  const float* x;           // feed [B][K] fp32 ...
+  const uint8_t* xu;        //   ... or, when non-null, uint8 pixels instead (K % 4 == 0, 4-byte aligned)
+  const float* ylab;        // labels [B][C]
+  float* W1;                // the graph's variables: [K][H], [H], [H][C], [C]
+  float* b1;
+  float* W2;
+  float* b2;
+  float* a2;                // scratch [BP][HP] each (BP = B, HP = H + 1, rounded up to 16)
+  float* dz2;
+  float* part;              // scratch of dtfk_graph_mlp_part_floats(B, H) floats, ZERO when first used
+  float* gW1;               // sgd == 0: gradient outputs, the variables' shapes
+  float* gb1;
+  float* gW2;
+  float* gb2;
+  float* metrics;           // [3] loss, accuracy, global_step after the step
+  float* host_metrics;      // the same three stored into pinned host memory by the last kernel, or null
+  void* gstep;              // the graph's global_step variable (gstep_kind.h), bumped once
+  int gstep_kind;
+  const float* lr;          // device learning rate (a captured step reads the current one)
+  int B, K, H, C;           // B <= 256, H <= 128, C <= 16, BP * HP <= 16384
+  int act, naive;           // act 0 sigmoid, 1 relu; naive: loss as -sum(y_ log softmax), else the stable form
+  int sgd;                  // 1: variables updated in place with lr; 0: gradients into g*
+};
+
+}  // namespace gmlp
 }  // namespace dtfk
 
 extern "C" {
@@ -101,10 +133,5 @@ int dtfk_mlpf_max_batch();
 hipError_t dtfk_mlp_persist_f32_launch(const dtfk::mlpf::Launch* p, hipStream_t stream);
 // ---- graph_mlp.hip
 long long dtfk_graph_mlp_part_floats(int B, int H);
-hipError_t dtfk_graph_feed_ingest(const void* host, void* dev, long long bytes, hipStream_t stream);
-hipError_t dtfk_graph_mlp_step(const float* x, const uint8_t* xu, const float* ylab, float* W1, float* b1, float* W2,
-                               float* b2, float* a2buf, float* dz2buf, float* part, float* gW1, float* gb1,
-                               float* gW2, float* gb2, float* metrics, float* host_metrics, void* gstep,
-                               int gstep_kind, const float* lr_ptr, int B, int K, int H, int C, int act, int naive,
-                               int sgd, hipStream_t stream);
+hipError_t dtfk_graph_mlp_step(const dtfk::gmlp::Step* p, hipStream_t stream);
 }

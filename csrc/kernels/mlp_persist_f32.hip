@@ -218,7 +218,7 @@ struct Args {
   long long* host_state;    // pinned: id of the launch that exited
   long long launch_id, run0, idle;
   unsigned census_tag;      // per-launch placement-census tag from the host (no device load in front of the census)
-  void* gvar;               // the graph's global_step variable (kind 0 none, 1 f32, 2 i64, 3 i32, 4 f64)
+  void* gvar;               // the graph's global_step variable and its dtype code (csrc/gstep_kind.h)
   int gvar_kind;
   unsigned* dctr;           // device: [0] records staged, [8] runs released, [16] stop, [32] steps done
   long long* res_ts;        // profiling only (DTF_RESIDENT_STAMPS): [run % 64][8] resident per-run stamps

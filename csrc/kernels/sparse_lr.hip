@@ -260,7 +260,7 @@ hipError_t dtfk_slr_stage(const void* src, void* dst, long long bytes, hipStream
   return hipGetLastError();
 }
 
-// gkind: 0 none, 1 f32, 2 i64, 3 i32, 4 f64 (the graph's global_step variable);
+// gkind: the dtype code of gvar, the graph's global_step variable (csrc/gstep_kind.h);
 // ids32: ids are int32 (the packed Session feed when every id < 2^31), else int64
 hipError_t dtfk_slr_step(float* W, long long F, const void* ids, int ids32, const long long* offsets,
                          const float* vals, const float* labels, float* bias, int B, const float* lr_ptr, float lr_val,

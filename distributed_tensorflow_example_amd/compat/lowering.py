@@ -298,6 +298,25 @@ class MLPStepPlan(_PlanBase):
         ctx.memo[id(self.pat.ylab)] = y
         return x, y
 
+    @staticmethod
+    def _shapes_ok(B, K, ny, W1, b1, W2, b2) -> bool:
+        """The kernels' shape gate (csrc/kernels/graph_mlp.hip) for a [B, K] feed
+        with ny label values, and fp32 variables."""
+        H, C = W1.shape[1], W2.shape[1]
+        HP, BP = (H + 16) // 16 * 16, (B + 15) // 16 * 16       # HP >= H + 1: the kernels' ones column
+        return (1 <= B <= 256 and BP * HP <= 16384 and H <= 128 and C <= 16 and W1.shape[0] == K
+                and ny == B * C and all(p.dtype == torch.float32 for p in (W1, b1, W2, b2)))
+
+    def _seed(self, memo, m, gs=None) -> None:
+        """This run's loss m[0] / accuracy m[1] (/ global_step `gs`, when given) and
+        the train op into the run's memo; their types are the caller's choice."""
+        memo[id(self.pat.loss)] = m[0]
+        if self.accuracy is not None:
+            memo[id(self.accuracy)] = m[1]
+        if gs is not None:
+            memo[id(self.info["global_step"])] = gs
+        memo[id(self.op)] = None
+
     # -------------------------------------------------------------- run
     def run(self, ctx, flat) -> bool:
         pat, info = self.pat, self.info
@@ -316,9 +335,8 @@ class MLPStepPlan(_PlanBase):
             return False
         B, K = x.shape
         H, C = W1.shape[1], W2.shape[1]
-        HP, BP = (H + 16) // 16 * 16, (B + 15) // 16 * 16       # HP >= H + 1: the kernels' ones column
-        if not (1 <= B <= 256 and BP * HP <= 16384 and H <= 128 and C <= 16 and W1.shape[0] == K
-                and y.numel() == B * C and all(p.dtype == torch.float32 for p in (W1, b1, W2, b2))):
+        HP, BP = (H + 16) // 16 * 16, (B + 15) // 16 * 16
+        if not self._shapes_ok(B, K, y.numel(), W1, b1, W2, b2):
             return False
         x = x.contiguous()
         y = y.reshape(B, C).contiguous()
@@ -380,16 +398,9 @@ class MLPStepPlan(_PlanBase):
         if needs:
             self.host_metrics.copy_(self.metrics)
             m = self.host_metrics
-            ctx.memo[id(pat.loss)] = m[0]
-            if self.accuracy is not None:
-                ctx.memo[id(self.accuracy)] = m[1]
-            if gs_seed:
-                ctx.memo[id(gs_var)] = m[2].to(gs_var.value.dtype)
+            self._seed(ctx.memo, m, m[2].to(gs_var.value.dtype) if gs_seed else None)
         else:
-            ctx.memo[id(pat.loss)] = self.metrics[0]
-            if self.accuracy is not None:
-                ctx.memo[id(self.accuracy)] = self.metrics[1]
-        ctx.memo[id(self.op)] = None
+            self._seed(ctx.memo, self.metrics)
         self.steps += 1
         return True
 
@@ -436,14 +447,8 @@ class MLPStepPlan(_PlanBase):
         if u8_ok and self._rplan is not None and self._rplan.run_u8(u8, fy2, float(opt._lr_value())):
             # the resident engine (compat/resident.py): no launch / completion per run
             ctx.resident_ran = True
-            m = self._rplan.out if scalars else torch.from_numpy(self._rplan.out.copy())
-            memo = ctx.memo
-            memo[id(pat.loss)] = m[0]
-            if self.accuracy is not None:
-                memo[id(self.accuracy)] = m[1]
-            if gs_seed:
-                memo[id(gs_var)] = self._rplan.out[2]
-            memo[id(self.op)] = None
+            out = self._rplan.out
+            self._seed(ctx.memo, out if scalars else torch.from_numpy(out.copy()), out[2] if gs_seed else None)
             self.steps += 1
             self.resident_steps = getattr(self, "resident_steps", 0) + 1
             return True
@@ -456,15 +461,10 @@ class MLPStepPlan(_PlanBase):
             self._cplan.run(fx if fx.flags.c_contiguous else np.ascontiguousarray(fx), fy2,
                             float(opt._lr_value()), bool(needs))
         # pinned host metrics [loss, accuracy, global_step]: numpy view -> float32
-        # scalar copies, or 0-d tensors when another node of the run consumes them
-        m = self._hm_np if scalars else self._cplan.host_metrics().clone()
-        memo = ctx.memo
-        memo[id(pat.loss)] = m[0]          # numpy float32 scalars (copies)
-        if self.accuracy is not None:
-            memo[id(self.accuracy)] = m[1]
-        if gs_seed:
-            memo[id(gs_var)] = self._hm_np[2]   # float32 global_step (gs_seed requires it)
-        memo[id(self.op)] = None
+        # scalar copies, or 0-d tensors when another node of the run consumes them;
+        # global_step always the float32 numpy scalar (gs_seed requires it)
+        self._seed(ctx.memo, self._hm_np if scalars else self._cplan.host_metrics().clone(),
+                   self._hm_np[2] if gs_seed else None)
         self.steps += 1
         return True
 
@@ -484,10 +484,8 @@ class MLPStepPlan(_PlanBase):
         pat = self.pat
         B, K = fx.shape
         H, C = W1.shape[1], W2.shape[1]
-        HP, BP = (H + 16) // 16 * 16, (B + 15) // 16 * 16
-        if not (1 <= B <= 256 and BP * HP <= 16384 and H <= 128 and C <= 16 and W1.shape[0] == K
-                and fy.size == B * C and all(p.dtype == torch.float32 and p.is_contiguous()
-                                             for p in (W1, b1, W2, b2))):
+        if not (self._shapes_ok(B, K, fy.size, W1, b1, W2, b2)
+                and all(p.is_contiguous() for p in (W1, b1, W2, b2))):
             return False
         gstep = None
         if gs_var is not None:

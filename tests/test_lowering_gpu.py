@@ -205,6 +205,110 @@ def test_uint8_feed_is_bit_identical(native):
         assert torch.equal(a, b)
 
 
+# The step plan at the ragged edges of its kernels: B = 17 (two row tiles, the
+# second holding one row), H = 5 (HP = 16) and H = 16 (HP = 32: the ones column
+# opens a new tile), C = 3, K = 20 (K % 4 == 0: the vector and uint8 loads, and
+# K + 1 spills into a second k-tile) and K = 7 (scalar loads, float feed only).
+_RB, _RC = 17, 3
+_RAGGED = [(20, 5), (20, 16), (7, 5), (7, 16)]
+
+
+def _ragged_params(K, H):
+    g = torch.Generator(device="cpu").manual_seed(K * 100 + H)
+    return [torch.randn(K, H, generator=g) * 0.3, torch.randn(H, generator=g) * 0.1,
+            torch.randn(H, _RC, generator=g) * 0.3, torch.randn(_RC, generator=g) * 0.1]
+
+
+def _ragged_batches(K, n):
+    """n batches as (uint8 pixels, the loader's float32 x = u8 / 255, one-hot y_)."""
+    rng = np.random.default_rng(K)
+    out = []
+    for _ in range(n):
+        u8 = rng.integers(0, 256, (_RB, K), dtype=np.uint8)
+        out.append((u8, u8.astype(np.float32) / np.float32(255.0),
+                    np.eye(_RC, dtype=np.float32)[rng.integers(0, _RC, _RB)]))
+    return out
+
+
+def _ragged_plan(native, K, H, gstep=None, use_graph=False):
+    dev = [t.cuda().contiguous() for t in _ragged_params(K, H)]
+    return native.GraphStepPlan(*dev, gstep, _RB, 0, True, use_graph), dev
+
+
+@pytest.mark.parametrize("K,H", _RAGGED)
+def test_step_plan_ragged_shapes_match_fp64(native, K, H):
+    """Three synchronous steps of GraphStepPlan.run against the fp64 graph: the
+    loss of every step and the final parameters to fp32 rounding (relative 1e-5);
+    where the uint8 feed applies (K % 4 == 0), run_u8 on the same pixels is
+    bit-identical to run."""
+    W1, b1, W2, b2 = _ragged_params(K, H)
+    ref = [p.numpy().astype(np.float64) for p in (W1, W2, b1, b2)]
+    plan, dev = _ragged_plan(native, K, H)
+    plan_u, dev_u = _ragged_plan(native, K, H) if K % 4 == 0 else (None, None)
+    for u8, x, y in _ragged_batches(K, 3):
+        ref, ref_ce, _ = _ref_step(ref, x, y, 0.5, "sigmoid", False)
+        plan.run(x, y, 0.5, True)
+        ce = float(plan.host_metrics()[0])
+        assert abs(ce - ref_ce) <= 1e-5 * abs(ref_ce), (ce, ref_ce)
+        if plan_u is not None:
+            plan_u.run_u8(u8, y, 0.5, True)
+            assert np.array_equal(plan.host_metrics().numpy(), plan_u.host_metrics().numpy())
+    for got, want in zip((dev[0], dev[2], dev[1], dev[3]), ref):
+        assert _rel(got.cpu().numpy(), want) < 1e-5
+    if plan_u is not None:
+        for a, b in zip(dev, dev_u):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("feed", ["f32", "u8"])
+def test_step_plan_unsynchronized_calls_match_synchronous(native, feed):
+    """The staging slots and their events: four calls that return without
+    waiting and a synchronizing fifth leave exactly what five synchronizing
+    calls leave, in the parameters and in the fifth step's host metrics."""
+    K, H = 20, 16
+    plan_s, dev_s = _ragged_plan(native, K, H)
+    plan_a, dev_a = _ragged_plan(native, K, H)
+    for i, (u8, x, y) in enumerate(_ragged_batches(K, 5)):
+        if feed == "u8":
+            plan_s.run_u8(u8, y, 0.5, True)
+            plan_a.run_u8(u8, y, 0.5, i == 4)
+        else:
+            plan_s.run(x, y, 0.5, True)
+            plan_a.run(x, y, 0.5, i == 4)
+    assert np.array_equal(plan_s.host_metrics().numpy(), plan_a.host_metrics().numpy())
+    for a, b in zip(dev_s, dev_a):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.int64, torch.int32, torch.float64, None],
+                         ids=["f32", "i64", "i32", "f64", "none"])
+@pytest.mark.parametrize("engine", ["direct", "captured", "sparse_lr"])
+def test_global_step_dtypes(native, engine, dtype):
+    """Every engine that bumps the graph's global_step takes it in each supported
+    dtype (and none at all): after three steps the variable holds 3 in its own
+    dtype, and the step plan's host metrics report 3.0 (0 without a variable)."""
+    gs = None if dtype is None else torch.zeros(1, dtype=dtype, device="cuda")
+    if engine == "sparse_lr":
+        W, bias = torch.zeros(8, 1, device="cuda"), torch.zeros(1, device="cuda")
+        plan = native.SparseLRPlan(W, bias, gs)
+        labels = torch.ones(1, device="cuda")                       # the smallest batch: one row, two features
+        offsets = torch.tensor([0, 2], dtype=torch.int64, device="cuda")
+        ids = torch.tensor([1, 6], dtype=torch.int64, device="cuda")
+        for _ in range(3):
+            plan.step(labels, offsets, ids, None, 0.5)
+        torch.cuda.synchronize()
+        assert plan.bad_ids() == 0
+    else:
+        K, H = 20, 5
+        plan, _ = _ragged_plan(native, K, H, gs, use_graph=engine == "captured")
+        assert plan.use_graph() == (engine == "captured")
+        for _, x, y in _ragged_batches(K, 3):
+            plan.run(x, y, 0.5, True)
+        assert float(plan.host_metrics()[2]) == (0.0 if gs is None else 3.0)
+    if gs is not None:
+        assert gs.dtype == dtype and gs.item() == 3
+
+
 def test_session_uses_uint8_feed_for_loader_batches(monkeypatch):
     """examples/mnist_example.py's graph fed by the MNIST loader: the lowered
     plan takes the uint8 path and matches a float-fed session bit for bit
