@@ -46,6 +46,10 @@ hipError_t dtfk_conv_wflip_multi(const long long* tab, const int* tiles, int nti
 long long dtfk_conv_wgrad_plan(int N, int H, int W, int C, int K, int stride, int ks, int* splits_out, int* sps_out);
 hipError_t dtfk_conv_wgrad(const void* dy, const void* x, float* dw, float* ws, int N, int H, int W, int C, int K,
                            int stride, int ks, int kcrs, hipStream_t stream);
+long long dtfk_conv3x3_dx2_tiles(int N, int H, int W);
+int dtfk_conv3x3_dx2_supported(int N, int H, int W, int C, int K);
+hipError_t dtfk_conv3x3_dx2(const void* dy, const void* wt, void* dx, float* part, int N, int H, int W, int C, int K,
+                            int bn, int accum, const void* bnx, const float* bnst, hipStream_t stream);
 hipError_t dtfk_bn_stat_partials(const void* x, float* part, int M, int C, hipStream_t st);
 hipError_t dtfk_bn_fwd_parts(const void* x, const void* res, const float* gamma, const float* beta, void* y,
                              const float* part, int P, float* mean, float* invstd, float* scale, float* shift,
@@ -258,6 +262,52 @@ void conv3x3_fwd(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Ten
      "conv_fwd");
 }
 
+// Input gradient of y = conv2d(x, w, stride 2, padding 1), w 3x3: dy [N, K, Ho, Wo],
+// wt [C, K, 3, 3] the flipped filter (conv3x3_wflip of w), dx [N, C, H, W] with
+// Ho = (H-1)/2+1, Wo = (W-1)/2+1.  accumulate: dx += the gradient.  bn_x / bn_stats
+// / part (EPI 2, as conv3x3_fwd): dx stored ReLU-masked, part [2, P, C] the BN
+// backward's partials, P = conv3x3_dx2_tiles(N, H, W).
+int64_t conv3x3_dx2_tiles(int64_t N, int64_t H, int64_t W) { return dtfk_conv3x3_dx2_tiles((int)N, (int)H, (int)W); }
+
+bool conv3x3_dx2_supported(at::Tensor dy, at::Tensor w, int64_t H, int64_t W) {
+  if (dy.dim() != 4 || ksize(w) != 3 || w.size(0) != dy.size(1) || H < 1 || W < 1) return false;
+  if (dy.size(2) != (H - 1) / 2 + 1 || dy.size(3) != (W - 1) / 2 + 1) return false;
+  return dtfk_conv3x3_dx2_supported((int)dy.size(0), (int)H, (int)W, (int)w.size(1), (int)w.size(0)) != 0;
+}
+
+void conv3x3_dx2(at::Tensor dy, at::Tensor wt, at::Tensor dx, c10::optional<at::Tensor> part, int64_t bn,
+                 bool accumulate, c10::optional<at::Tensor> bn_x, c10::optional<at::Tensor> bn_stats) {
+  cl_bf16(dy, "conv3x3_dx2 dy");
+  cl_bf16(wt, "conv3x3_dx2 wt");
+  cl_bf16(dx, "conv3x3_dx2 dx");
+  const int N = (int)dx.size(0), C = (int)dx.size(1), H = (int)dx.size(2), W = (int)dx.size(3), K = (int)dy.size(1);
+  if (ksize(wt) != 3 || wt.size(0) != C || wt.size(1) != K || dy.size(0) != N || dy.size(2) != (H - 1) / 2 + 1 ||
+      dy.size(3) != (W - 1) / 2 + 1)
+    throw std::runtime_error("conv3x3_dx2: shapes");
+  float* pp = nullptr;
+  if (part.has_value()) {
+    const int64_t P = dtfk_conv3x3_dx2_tiles(N, H, W);
+    if (!part->is_cuda() || part->scalar_type() != at::kFloat || !part->is_contiguous() || part->numel() < 2 * P * C)
+      throw std::runtime_error("conv3x3_dx2: part must hold [2, P, C] fp32");
+    pp = part->data_ptr<float>();
+  }
+  const void* bx = nullptr;
+  const float* bst = nullptr;
+  if (bn_x.has_value()) {
+    cl_bf16(*bn_x, "conv3x3_dx2 bn_x");
+    if (!bn_stats.has_value() || pp == nullptr || accumulate || bn_x->sizes() != dx.sizes())
+      throw std::runtime_error("conv3x3_dx2: bn_x needs bn_stats, part and dx's shape, and no accumulate");
+    f32(*bn_stats, 4LL * C, "bn_stats");
+    bx = bn_x->data_ptr();
+    bst = bn_stats->data_ptr<float>();
+  } else if (pp != nullptr) {
+    throw std::runtime_error("conv3x3_dx2: part needs bn_x");
+  }
+  ck(dtfk_conv3x3_dx2(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), pp, N, H, W, C, K, (int)bn, accumulate ? 1 : 0, bx,
+                      bst, cs()),
+     "conv3x3_dx2");
+}
+
 // wt [C, K, ks, ks] channels_last = the flipped, transposed filter of the stride-1 input gradient
 void conv3x3_wflip(at::Tensor w, at::Tensor wt) {
   cl_bf16(w, "conv_wflip w");
@@ -348,6 +398,11 @@ void init_bn(pybind11::module& m) {
   m.def("conv3x3_fwd", &conv3x3_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("part") = py::none(),
         py::arg("stride") = 1, py::arg("bn") = 0, py::arg("accumulate") = false, py::arg("bn_x") = py::none(),
         py::arg("bn_stats") = py::none(), py::arg("bn_res") = py::none());
+  m.def("conv3x3_dx2", &conv3x3_dx2, py::arg("dy"), py::arg("wt"), py::arg("dx"), py::arg("part") = py::none(),
+        py::arg("bn") = 0, py::arg("accumulate") = false, py::arg("bn_x") = py::none(),
+        py::arg("bn_stats") = py::none());
+  m.def("conv3x3_dx2_tiles", &conv3x3_dx2_tiles);
+  m.def("conv3x3_dx2_supported", &conv3x3_dx2_supported);
   m.def("conv3x3_wflip", &conv3x3_wflip);
   m.def("conv_wflip_multi", &conv_wflip_multi);
   m.def("strided_add", &strided_add);

@@ -1,4 +1,4 @@
-// Reached by: ops/conv.py ShadowConv2d (ResNet-50 convolutions); tests/test_conv_igemm_gpu.py
+// Reached by: ops/conv.py ShadowConv2d (ResNet-50 convolutions); tests/test_conv_igemm_gpu.py, tests/test_conv_dx_stride2_gpu.py
 // 3x3 (pad 1) and 1x1 (pad 0) convolutions, stride 1 or 2, on NHWC bf16
 // activations as implicit GEMMs on the gfx950 matrix cores, with an optional
 // BatchNorm statistics epilogue (ResNet-50, BASELINE.json configs[2]).  KS is
@@ -38,6 +38,20 @@
 // The input gradient of a stride-1 conv is the same convolution of dy with the
 // flipped, channel-transposed filter (wflip; wflip_multi re-flips every conv's
 // filter in one launch after an optimizer step, ops/conv.py _flipped).  The
+// input gradient of a stride-2 3x3 conv is not a convolution of dy, but it is
+// one per parity class of the input pixel (DX2, dtfk_conv3x3_dx2):
+//
+//   dx[n, h, w, c] = sum over (r, s) with h+1-r, w+1-s even, and k:
+//                    dy[n, (h+1-r)/2, (w+1-s)/2, k] * w[k][r][s][c]
+//
+// An even h takes r = 1 only, an odd h r = 0 and 2 (w likewise): the classes
+// (h%2, w%2) have 1, 2, 2 and 4 taps -- 9 taps per 4 pixels, the forward's
+// FLOPs.  GEMM rows are the input pixels class by class, (n, h/2, w/2) within
+// a class, each class padded to whole 128-row tiles so that a workgroup has
+// one tap set (a wave-uniform K loop of taps * K/64 steps); the 4-tap tiles
+// are dispatched first, the 1-tap ones last.  The B operand is the same
+// flipped filter at tap (2-r, 2-s); the epilogue addresses each row by its
+// pixel.  Every input pixel has an in-range tap, so all of dx is written.  The
 // weight gradient (conv_wgrad) is split over pixels into fp32 slabs summed in
 // split order by wgrad_reduce (profiles/conv_wgrad_sweep_r5.txt).
 #include "common.h"
@@ -55,6 +69,17 @@ constexpr int OOB = 0x7ffffff0;
 
 __device__ __forceinline__ int swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
 
+// DX2: 128-row tiles of the four parity classes of an [N, H, W] input, in
+// dispatch order (h%2, w%2) = (1,1), (1,0), (0,1), (0,0)
+__host__ __device__ inline void dx2_class_tiles(int N, int H, int W, int t[4]) {
+  const int he = (H + 1) / 2, ho = H / 2, we = (W + 1) / 2, wo = W / 2;   // even / odd rows and columns
+  auto tiles = [N](int h, int w) { return (int)(((long long)N * h * w + BM - 1) / BM); };
+  t[0] = tiles(ho, wo);
+  t[1] = tiles(ho, we);
+  t[2] = tiles(he, wo);
+  t[3] = tiles(he, we);
+}
+
 // EPI: 0 plain, 1 BN statistics of y (forward), 2 BN backward of the BatchNorm
 // whose OUTPUT gradient y is (an input gradient feeding BN(+ReLU)'s backward):
 // y is stored as g = y * relu'(bn(bnx)) and part receives the per-channel sums
@@ -67,13 +92,16 @@ __device__ __forceinline__ int swz(int row, int ch) { return ch ^ ((row >> 1) & 
 // ONE: a single 64-channel K step (1x1 over C = 64): one operand buffer, the
 // LDS sized for the epilogue, three workgroups per CU instead of two -- the
 // load -> MFMA -> epilogue chain of such a tile is latency bound.
+// DX2: the input gradient of a stride-2 3x3 conv (header comment): x is dy
+// [N, H, W, C], w the flipped filter, y is dx [N, Ho, Wo, K] with H = (Ho-1)/2+1,
+// W = (Wo-1)/2+1; blockIdx.x runs over the class tiles (EPI 0 or 2, no xcd).
 template <int KS, int BN, int EPI>
 constexpr int fwd_lds_bytes(bool one) {
   constexpr int BUF = BM * BK * 2 + BN * BK * 2, PITCH = BN * 2 + 16;
   constexpr int EPI_B = ((BM * PITCH + 15) & ~15) + (EPI >= 2 ? NTHR * 16 * 4 : (EPI == 1 ? 2 * NTHR * 4 : 0));
   return one ? (BUF > EPI_B ? BUF : EPI_B) : 2 * BUF;
 }
-template <int KS, int BN, int EPI, bool ONE = false>
+template <int KS, int BN, int EPI, bool ONE = false, bool DX2 = false>
 __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
                                                     uint16_t* __restrict__ y, float* __restrict__ part, int N,
                                                     int H, int W, int C, int K, int Ho, int Wo, int stride,
@@ -89,7 +117,8 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
   __shared__ __attribute__((aligned(16))) uint8_t smem[fwd_lds_bytes<KS, BN, EPI>(ONE)];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1;
-  const long long M = (long long)N * Ho * Wo;
+  static_assert(!DX2 || (KS == 3 && !ONE && (EPI == 0 || EPI == 2)), "DX2: 3x3, plain or BN-backward epilogue");
+  const long long Mpix = (long long)N * Ho * Wo;   // output pixels
   // xcd: the channel tiles of one pixel tile (they share its A rows) on one XCD,
   // consecutive pixel tiles dealt over the 8 XCDs (1-D grid, ids round robin)
   int bx, by;
@@ -102,7 +131,27 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
     bx = blockIdx.x;
     by = blockIdx.y;
   }
-  const long long m0 = (long long)bx * BM;
+  // rows of this tile's GEMM: all output pixels, or (DX2) the pixels (n, 2h'+ph, 2w'+pw)
+  // of its parity class over the class's [N, Hc, Wc] sub-grid, tile tl of the class
+  int ph = 0, pw = 0, Hc = Ho, Wc = Wo, tl = bx, ptiles = 0;
+  if constexpr (DX2) {
+    int ct[4];
+    dx2_class_tiles(N, Ho, Wo, ct);
+    ptiles = ct[0] + ct[1] + ct[2] + ct[3];
+    int cls = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      if (cls == i && tl >= ct[i]) {
+        tl -= ct[i];
+        cls = i + 1;
+      }
+    ph = cls < 2;
+    pw = cls == 0 || cls == 2;
+    Hc = ph ? Ho / 2 : (Ho + 1) / 2;
+    Wc = pw ? Wo / 2 : (Wo + 1) / 2;
+  }
+  const long long M = DX2 ? (long long)N * Hc * Wc : Mpix;
+  const long long m0 = (long long)tl * BM;
   const int k0 = by * BN;
 
   // this thread's 4 A rows (pixel coordinates fixed over the K loop) and chunk
@@ -114,16 +163,16 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
     const long long m = m0 + (tid >> 3) + 32 * i;
     arow[i] = m < M;
     const long long mm = arow[i] ? m : 0;
-    awo[i] = (int)(mm % Wo);
-    const long long t = mm / Wo;
-    aho[i] = (int)(t % Ho);
-    an[i] = (int)(t / Ho);
+    awo[i] = (int)(mm % Wc);
+    const long long t = mm / Wc;
+    aho[i] = (int)(t % Hc);
+    an[i] = (int)(t / Hc);
   }
   const auto xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(x), 0, (int)(xbytes > 0x7ffffff0 ? 0x7ffffff0 : xbytes), 0x00020000);
   const long long wbytes = (long long)K * TAPS * C * 2;
   const auto wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(w), 0, (int)wbytes, 0x00020000);
   const int ncc = C / BK;
-  const int nsteps = TAPS * ncc;
+  const int nsteps = (DX2 ? (ph + 1) * (pw + 1) : TAPS) * ncc;
 
   // two register sets: a step's operands are loaded two steps ahead (issued
   // while the step before it is multiplied), so one HBM round trip hides
@@ -131,11 +180,21 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
   u32x4 ra[2][4], rb[2][NB];
   auto load = [&](int step, auto pc) {
     constexpr int P = decltype(pc)::value;
-    const int rs = step / ncc, c0 = (step % ncc) * BK;
+    int rs = step / ncc;
+    const int c0 = (step % ncc) * BK;
     const int r = rs / KS, s = rs % KS;
+    int dh = 0, dw = 0;
+    if constexpr (DX2) {
+      // tap rs of the class -> filter row qr = 1 (even h) or 0 / 2 (odd h), qs likewise;
+      // its dy pixel is (h' + (qr == 0), w' + (qs == 0)), its flipped-filter tap (2-qr, 2-qs)
+      const int qr = ph ? 2 * (pw ? rs >> 1 : rs) : 1, qs = pw ? 2 * (rs & 1) : 1;
+      dh = qr == 0;
+      dw = qs == 0;
+      rs = (2 - qr) * KS + 2 - qs;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int hi = aho[i] * stride + r - PAD, wi = awo[i] * stride + s - PAD;
+      const int hi = DX2 ? aho[i] + dh : aho[i] * stride + r - PAD, wi = DX2 ? awo[i] + dw : awo[i] * stride + s - PAD;
       const bool ok = arow[i] && hi >= 0 && hi < H && wi >= 0 && wi < W;
       const long long off = ((((long long)an[i] * H + hi) * W + wi) * C + c0 + 8 * ach) * 2;
       ra[P][i] = __builtin_amdgcn_raw_buffer_load_b128(xr, ok ? (int)off : OOB, 0, 0);
@@ -183,6 +242,15 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
   // (not in the single-step variant: its 3-workgroup register budget spills)
   constexpr bool POST3 = BNR && !PRE3 && !ONE;
   u32x4 pre[EIT], pre_y[PRE3 || POST3 ? EIT : 1], pre_r[PRE3 || POST3 ? EIT : 1];
+  // element offset in y of GEMM row m (DX2: the row's pixel of its class)
+  auto yrow = [&](long long m) -> long long {
+    if constexpr (DX2) {
+      const int wq = (int)m % Wc, t = (int)m / Wc;
+      return (((long long)(t / Hc) * Ho + 2 * (t % Hc) + ph) * Wo + 2 * wq + pw) * K;
+    } else {
+      return m * K;
+    }
+  };
   auto prefetch = [&]() {
     if (!(BNB || accum)) return;
     const uint16_t* src = BNB ? bnx : y;
@@ -191,7 +259,7 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
       const int t = tid + it * NTHR;
       const long long m = m0 + t / CPR;
       if (m < M) {
-        const long long e = m * K + k0 + 8 * (t % CPR);
+        const long long e = yrow(m) + k0 + 8 * (t % CPR);
         pre[it] = *reinterpret_cast<const u32x4*>(src + e);
         if constexpr (PRE3) {
           pre_y[it] = *reinterpret_cast<const u32x4*>(y + e);
@@ -256,7 +324,7 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
       const int t = tid + it * NTHR;
       const long long m = m0 + t / CPR;
       if (m < M) {
-        const long long e = m * K + k0 + 8 * (t % CPR);
+        const long long e = yrow(m) + k0 + 8 * (t % CPR);
         pre_y[it] = *reinterpret_cast<const u32x4*>(y + e);
         pre_r[it] = *reinterpret_cast<const u32x4*>(bnres + e);
       }
@@ -304,7 +372,7 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
         const u32x4 xo = pre[it];
         u32x4 ro = {0u, 0u, 0u, 0u};
         if constexpr (BNR) {   // the complete gradient: conv + the folded residual gradient (rounded as stored)
-          const long long e = m * K + k0 + 8 * ch;
+          const long long e = yrow(m) + k0 + 8 * ch;
           constexpr bool HELD = PRE3 || POST3;
           const u32x4 o = HELD ? pre_y[HELD ? it : 0] : *reinterpret_cast<const u32x4*>(y + e);
           ro = HELD ? pre_r[HELD ? it : 0] : *reinterpret_cast<const u32x4*>(bnres + e);
@@ -330,7 +398,7 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
         for (int q = 0; q < 4; ++q)
           v[q] = pack2bf(bf2f(v[q] & 0xffff) + bf2f(o[q] & 0xffff), bf2f(v[q] >> 16) + bf2f(o[q] >> 16));
       }
-      *reinterpret_cast<u32x4*>(y + m * K + k0 + 8 * ch) = v;
+      *reinterpret_cast<u32x4*>(y + yrow(m) + k0 + 8 * ch) = v;
     }
   }
   if constexpr (BNB) {
@@ -350,7 +418,7 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
         a += red[j * 16 + q];
         b += red[j * 16 + 8 + q];
       }
-      const int P = (int)((M + BM - 1) / BM);
+      const int P = DX2 ? ptiles : (int)((M + BM - 1) / BM);
       part[((size_t)0 * P + bx) * K + k0 + tid] = a;
       part[((size_t)1 * P + bx) * K + k0 + tid] = b;
     }
@@ -820,6 +888,52 @@ long long dtfk_conv_tiles(int N, int H, int W, int stride, int ks) {
   return ((long long)N * conv_out(H, stride, ks) * conv_out(W, stride, ks) + dtfk::cig::BM - 1) / dtfk::cig::BM;
 }
 long long dtfk_conv3x3_tiles(int N, int H, int W, int stride) { return dtfk_conv_tiles(N, H, W, stride, 3); }
+
+// ---- input gradient of y = conv3x3(x, w, stride 2, pad 1): x is [N, H, W, C], dy [N, Ho, Wo, K]
+// row tiles over the four parity classes: the P of the [2, P, C] partials
+long long dtfk_conv3x3_dx2_tiles(int N, int H, int W) {
+  int t[4];
+  dtfk::cig::dx2_class_tiles(N, H, W, t);
+  return (long long)t[0] + t[1] + t[2] + t[3];
+}
+int dtfk_conv3x3_dx2_supported(int N, int H, int W, int C, int K) {
+  if (N < 1 || H < 1 || W < 1 || C < 64 || K < 64 || C % 64 != 0 || K % 64 != 0) return 0;
+  const long long dybytes = (long long)N * conv_out(H, 2, 3) * conv_out(W, 2, 3) * K * 2;
+  const long long dxbytes = (long long)N * H * W * C * 2;
+  if (dybytes >= 0x7ffffff0LL || dxbytes >= 0x7ffffff0LL || 9LL * K * C * 2 >= 0x7ffffff0LL) return 0;   // 32-bit offsets
+  return 1;
+}
+// dx = the gradient (+ dx when accum); wt: the flipped filter [C][3][3][K] (dtfk_conv_wflip).
+// bnx / bnst (EPI 2, with part [2, P, C], not with accum): dx is the output gradient of a
+// BatchNorm + ReLU whose input was bnx; dx is stored ReLU-masked and part receives that BN
+// backward's partials.  part without bnx (EPI 1) and a residual BN (EPI 3) are invalid here.
+hipError_t dtfk_conv3x3_dx2(const void* dy, const void* wt, void* dx, float* part, int N, int H, int W, int C, int K,
+                            int bn, int accum, const void* bnx, const float* bnst, hipStream_t stream) {
+  using namespace dtfk::cig;
+  if (!dtfk_conv3x3_dx2_supported(N, H, W, C, K)) return hipErrorInvalidValue;
+  if ((part != nullptr) != (bnx != nullptr) || (bnx != nullptr && (bnst == nullptr || accum)))
+    return hipErrorInvalidValue;
+  const long long tiles = dtfk_conv3x3_dx2_tiles(N, H, W);
+  if (bn != 64 && bn != 128) bn = (C % 128 == 0 && tiles * (C / 128) >= 256) ? 128 : 64;   // as dtfk_conv_fwd
+  if (C % bn) return hipErrorInvalidValue;
+  const int Hy = conv_out(H, 2, 3), Wy = conv_out(W, 2, 3);
+  const dim3 grid((unsigned)tiles, (unsigned)(C / bn));
+  const long long dybytes = (long long)N * Hy * Wy * K * 2;
+  auto ds = static_cast<const uint16_t*>(dy);
+  auto ws = static_cast<const uint16_t*>(wt);
+  auto xs = static_cast<uint16_t*>(dx);
+  auto bx = static_cast<const uint16_t*>(bnx);
+  // the kernel's view: operand dy [N, Hy, Wy, K] (its x, C), output dx [N, H, W, C] (its y, K)
+#define DTFK_DX2(BNV, EP)                                                                                          \
+  hipLaunchKernelGGL((conv_fwd<3, BNV, EP, false, true>), grid, dim3(NTHR), 0, stream, ds, ws, xs, part, N, Hy, Wy, \
+                     K, C, H, W, 2, dybytes, accum, bx, bnst, static_cast<const uint16_t*>(nullptr), 0)
+  if (bn == 128 && bnx) { DTFK_DX2(128, 2); }
+  else if (bn == 128) { DTFK_DX2(128, 0); }
+  else if (bnx) { DTFK_DX2(64, 2); }
+  else { DTFK_DX2(64, 0); }
+#undef DTFK_DX2
+  return hipGetLastError();
+}
 
 hipError_t dtfk_conv_wflip(const void* w, void* wt, int K, int C, int ks, hipStream_t stream) {
   const long long n = (long long)K * ks * ks * C;

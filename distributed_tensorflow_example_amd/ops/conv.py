@@ -1,16 +1,21 @@
 """Conv2d on the optimizer-maintained bf16 weight shadow, with a sunk wgrad.
 
-The convolutions themselves stay on MIOpen (its implicit-GEMM MFMA solvers,
-picked by solver search when `torch.backends.cudnn.benchmark` is on); what
-this removes is the glue around them in a bf16-compute / fp32-master step:
+Each product of a convolution (forward, input gradient, weight gradient) runs
+on an in-tree engine where one takes its shape -- the GEMMs for 1x1, the
+implicit GEMM of `csrc/kernels/conv_igemm.hip` for 3x3 and the strided 1x1
+projection -- and on MIOpen (its implicit-GEMM MFMA solvers, picked by solver
+search when `torch.backends.cudnn.benchmark` is on) otherwise, or where a
+one-time timing on the layer's own operands finds MIOpen faster.  Around the
+products, in a bf16-compute / fp32-master step:
 
 * forward reads `weight._shadow` (bf16, same channels_last layout), which the
   fused optimizer rewrites in the same pass that updates the fp32 master --
   no per-step fp32->bf16 weight cast;
-* backward asks MIOpen for (dx, dW) in one `convolution_backward` call and,
-  when the weight is managed by DDP (ops.grad_sink), folds the bf16 dW into
-  the fp32 bucket view with one mixed-dtype add -- no bf16->fp32 cast pass and
-  no separate AccumulateGrad add;
+* whatever of (dx, dW) stays on MIOpen comes from one `convolution_backward`
+  call; when the weight is managed by DDP (ops.grad_sink) the weight gradient
+  goes into the fp32 bucket view -- the in-tree engines accumulate into it
+  directly, MIOpen's bf16 dW with a cast and an add -- and no separate
+  AccumulateGrad add runs;
 * a 1x1 / stride-1 convolution on NHWC activations is a plain GEMM over the
   rows: y[NHW, cout] = x[NHW, cin] W^T, dx = dy W, dW = dy^T x.  Each of the
   three products picks, per shape and once (timed on the layer's own
@@ -23,11 +28,15 @@ this removes is the glue around them in a bf16-compute / fp32-master step:
   profiles/resnet50_r4.md).  `DTF_CONV_GEMM`: auto (default) / never.
 * a 3x3 / pad-1 / stride-1-or-2 convolution with 64-multiple channel counts
   may run on the in-tree implicit-GEMM kernel (`csrc/kernels/conv_igemm.hip`,
-  MFMA, no im2col buffer): its forward, and for stride 1 its input gradient
-  (the same convolution of dy with the flipped, channel-transposed filter),
-  each chosen per shape against MIOpen by the same one-time timing.  The
-  kernel can also emit the BatchNorm statistics partials of its output
-  (`conv3x3(..., stats=)`).  `DTF_CONV_IGEMM`: auto (default) / never / always.
+  MFMA, no im2col buffer): its forward, its weight gradient and, at both
+  strides, its input gradient -- at stride 1 the same convolution of dy with
+  the flipped, channel-transposed filter, at stride 2 one such product per
+  parity class of the input pixel on the same flipped filter (9 taps per 4
+  pixels; `DTF_CONV_DX_S2=0` keeps it on MIOpen) -- each chosen per shape
+  against MIOpen by the same one-time timing.  The kernel can also emit the
+  BatchNorm statistics partials of its output (`conv3x3(..., stats=)`), and an
+  input gradient feeding a BatchNorm + ReLU backward that BN's partials
+  (`conv3x3_dx(..., bnb=)`).  `DTF_CONV_IGEMM`: auto (default) / never / always.
 * BatchNorm statistics hand-off (`DTF_CONV_BN_STATS`, default on): the 3x3
   kernel and the 1x1 gemm_big forward (`dtfk_gemm_bn_stats`) write the
   per-channel sum / sum-of-squares partials of their output in the epilogue;
@@ -57,6 +66,9 @@ _BN_STATS = os.environ.get("DTF_CONV_BN_STATS", "1") != "0"
 # ResNet-50 9,391-9,413 vs 9,258-9,302 img/s same box, scripts/sessions/gpu_r6q.sh),
 # or gather the strided pixels once and run them as GEMMs over the copy (1)
 _S2_GATHER = os.environ.get("DTF_CONV_S2_GATHER", "0") != "0"
+# stride-2 3x3 input gradients on the in-tree kernel (conv_igemm.hip DX2), chosen per
+# shape against MIOpen; 0 keeps them on MIOpen (the A/B switch)
+_DX_S2 = os.environ.get("DTF_CONV_DX_S2", "1") != "0"
 _handoff = {}   # id(conv output) -> (partials, P): from _ShadowConv.forward to ShadowConv2d.forward
 _choice: dict = {}
 _timings: dict = {}
@@ -245,27 +257,47 @@ def _bnb_fits(bnb, into, x_shape) -> bool:
             and bnb.res.is_contiguous(memory_format=torch.channels_last))
 
 
-def conv3x3_dx(dy, w16, x_shape, into=None, bnb=None):
+def conv3x3_dx(dy, w16, x_shape, into=None, bnb=None, stride: int = 1, bn: int = 0):
     """Input gradient of a stride-1 3x3 (or 1x1) conv: the same convolution of
     dy with the flipped, channel-transposed filter; `into` (a channels_last bf16
     gradient of x from another branch) is accumulated in the epilogue.  `bnb`
     (ops.bn.BwdSlot of the BatchNorm (+ residual) + ReLU that produced x): dx
     is returned ReLU-masked and the epilogue writes that BN backward's partials
     into the slot, so the BN's backward skips its own pass over the gradient
-    (with a residual BN, `into` must be the residual branch's gradient)."""
+    (with a residual BN, `into` must be the residual branch's gradient).
+    `stride` 2 (3x3 only): the same products per parity class of the input
+    pixel, on the same flipped filter (conv_igemm.hip DX2); a residual `bnb`
+    is left to the BN's own pass.  `bn`: the channel tile width (0 = the
+    kernel's choice)."""
+    if stride == 2:
+        if w16.shape[2] != 3 or w16.shape[3] != 3:
+            raise ValueError("conv3x3_dx: stride 2 takes a 3x3 filter")
+        wt = _flipped(w16)
+        if bnb is not None and bnb.res is None and _bnb_fits(bnb, into, x_shape):
+            P = int(_C().conv3x3_dx2_tiles(x_shape[0], x_shape[2], x_shape[3]))
+            part = torch.empty((2, P, x_shape[1]), device=dy.device, dtype=torch.float32)
+            dx = _cl_empty(x_shape[0], x_shape[1], x_shape[2], x_shape[3], dy)
+            _C().conv3x3_dx2(dy, wt, dx, part, bn, False, bnb.x, bnb.stats)
+            bnb.part, bnb.g, bnb.g_version = (part, P), dx, dx._version
+            return dx
+        dx = into if into is not None else _cl_empty(x_shape[0], x_shape[1], x_shape[2], x_shape[3], dy)
+        _C().conv3x3_dx2(dy, wt, dx, None, bn, into is not None)
+        return dx
+    if stride != 1:
+        raise ValueError("conv3x3_dx: stride 1 or 2")
     wt = _flipped(w16)
     if _bnb_fits(bnb, into, x_shape):
         P = conv3x3_stat_rows(dy, 1)
         part = torch.empty((2, P, x_shape[1]), device=dy.device, dtype=torch.float32)
         dx = into if into is not None else _cl_empty(x_shape[0], x_shape[1], x_shape[2], x_shape[3], dy)
-        conv3x3(dy, wt, 1, stats=part, out=dx, accumulate=into is not None, bn_x=bnb.x, bn_stats=bnb.stats,
+        conv3x3(dy, wt, 1, stats=part, out=dx, bn=bn, accumulate=into is not None, bn_x=bnb.x, bn_stats=bnb.stats,
                 bn_res=bnb.res)
         bnb.part, bnb.g, bnb.g_version = (part, P), dx, dx._version
         return dx
     if into is not None:
-        return conv3x3(dy, wt, 1, out=into, accumulate=True)
+        return conv3x3(dy, wt, 1, out=into, bn=bn, accumulate=True)
     dx = _cl_empty(x_shape[0], x_shape[1], x_shape[2], x_shape[3], dy)
-    return conv3x3(dy, wt, 1, out=dx)
+    return conv3x3(dy, wt, 1, out=dx, bn=bn)
 
 
 def _fuse_bnb(bnb, dx_eng, key, x) -> bool:
@@ -332,16 +364,16 @@ def _fwd3_engine(x, w16, stride: int) -> str:
     return _choice[("fwd3",) + key]
 
 
-def _dx3_engine(dy, x, w16) -> str:
+def _dx3_engine(dy, x, w16, stride: int = 1) -> str:
     if _IGEMM == "always":
         return "igemm"
-    key = (tuple(x.shape), w16.shape[0], 1)
+    key = (tuple(x.shape), w16.shape[0], stride)
     if ("dx3",) + key not in _choice:
         if _POLICY == "never":
             return "miopen"
         return _pick("dx3", key, {"miopen": lambda: torch.ops.aten.convolution_backward(
-                         dy, x, w16, None, (1, 1), (1, 1), (1, 1), False, [0, 0], 1, [True, False, False]),
-                     "igemm": lambda: conv3x3_dx(dy, w16, x.shape)})
+                         dy, x, w16, None, (stride, stride), (1, 1), (1, 1), False, [0, 0], 1, [True, False, False]),
+                     "igemm": lambda: conv3x3_dx(dy, w16, x.shape, stride=stride)})
     return _choice[("dx3",) + key]
 
 
@@ -540,8 +572,13 @@ class _ShadowConv(torch.autograd.Function):
         gw = (ctx.gemm or xs is not None) and dy.is_contiguous(memory_format=torch.channels_last)
         dx_eng = _dx_engine(dy, x, w16) if gemm and need_x else "miopen"
         dw_eng = _dw_engine(dy, xw, w16) if gw and need_w else "miopen"
-        dx3 = (_dx3_engine(dy, x, w16) if need_x and getattr(ctx, "igemm", False) and tuple(stride) == (1, 1)
-               and dy.is_contiguous(memory_format=torch.channels_last) else "miopen")
+        # the in-tree input gradient: stride 1 (3x3 or 1x1), or a stride-2 3x3 (ctx.igemm also
+        # holds for the stride-2 1x1 projection, whose input gradient stays a strided GEMM)
+        s3 = int(stride[0])
+        dx3_ok = (need_x and getattr(ctx, "igemm", False) and dy.is_contiguous(memory_format=torch.channels_last)
+                  and (s3 == 1 or (_DX_S2 and tuple(stride) == (2, 2) and w16.shape[2] == 3
+                                   and bool(_C().conv3x3_dx2_supported(dy, w16, x.shape[2], x.shape[3])))))
+        dx3 = _dx3_engine(dy, x, w16, s3) if dx3_ok else "miopen"
         dw3 = (_dw3_engine(dy, x, w16, int(stride[0])) if need_w and getattr(ctx, "igemm", False)
                and dy.is_contiguous(memory_format=torch.channels_last) else "miopen")
         extra = ctx.slot.take() if ctx.slot is not None else None   # a residual branch's gradient of x
@@ -551,7 +588,8 @@ class _ShadowConv(torch.autograd.Function):
         # partials from this input gradient's epilogue (not for a shared x: the
         # pair's other gradient would be missing from the mask's input)
         bnb = ctx.bnb if share is None else None
-        bnb_ok = need_x and bnb is not None and not strided and _bnb_fits(bnb, extra, x.shape)
+        bnb_ok = (need_x and bnb is not None and not strided and _bnb_fits(bnb, extra, x.shape)
+                  and (s3 == 1 or bnb.res is None))    # stride 2: no residual epilogue, that BN runs its own pass
         fuse1 = (bnb_ok and dx3 != "igemm" and gemm and igemm1_ok(x, w16)
                  and _fuse_bnb(bnb, dx_eng, (tuple(x.shape), w16.shape[0]), x))
         # MIOpen's share: one convolution_backward call for whatever stays on it
@@ -571,9 +609,9 @@ class _ShadowConv(torch.autograd.Function):
                 _C().strided_add(extra, comp, stride[0])
                 dx = extra
         elif need_x and dx3 == "igemm" and bnb_ok:
-            dx = conv3x3_dx(dy, w16, x.shape, into=extra, bnb=bnb)
+            dx = conv3x3_dx(dy, w16, x.shape, into=extra, bnb=bnb, stride=s3)
         elif need_x and dx3 == "igemm":
-            dx = conv3x3_dx(dy, w16, x.shape)
+            dx = conv3x3_dx(dy, w16, x.shape, stride=s3)
             if extra is not None:
                 dx = dx.add_(extra)
         elif fuse1:

@@ -1,7 +1,8 @@
 """ResNet-50 (B=128) 3x3 convolutions: in-tree implicit GEMM
 (csrc/kernels/conv_igemm.hip) vs MIOpen -- forward, weight gradient (into an
-fp32 buffer; MIOpen's bf16 result plus the add) and stride-1 input gradient,
-us per call.  One JSON line per shape.
+fp32 buffer; MIOpen's bf16 result plus the add) and input gradient (stride 1
+and stride 2, plain and with the BN-backward epilogue), us per call.  One JSON
+line per shape.
 
     python scripts/probes/conv3x3_paths.py [batch]
 """
@@ -17,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 def main():
     from distributed_tensorflow_example_amd.ops import big_gemm, conv
+    from distributed_tensorflow_example_amd.ops.bn import BwdSlot
 
     torch.backends.cudnn.benchmark = True
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
@@ -42,11 +44,18 @@ def main():
         r["dw_miopen_us"] = round(big_gemm._time(lambda: acc.add_(torch.ops.aten.convolution_backward(
             dyo, x, w, None, (s, s), (1, 1), (1, 1), False, [0, 0], 1, [False, True, False])[1]), reps=10) * 1e3, 1)
         r["dw_igemm_us"] = round(big_gemm._time(lambda: conv.conv3x3_dw(dyo, x, s, into=acc), reps=10) * 1e3, 1)
-        if s == 1:
-            dy = torch.randn(B, K, H, H, device="cuda").bfloat16().contiguous(memory_format=torch.channels_last)
-            r["dx_miopen_us"] = round(big_gemm._time(lambda: torch.ops.aten.convolution_backward(
-                dy, x, w, None, (1, 1), (1, 1), (1, 1), False, [0, 0], 1, [True, False, False]), reps=10) * 1e3, 1)
-            r["dx_igemm_us"] = round(big_gemm._time(lambda: conv.conv3x3_dx(dy, w, x.shape), reps=10) * 1e3, 1)
+        # input gradient at both strides (stride 2: the parity-class mode), and with the
+        # BN-backward epilogue (EPI 2) against a dummy BatchNorm + ReLU over x
+        r["dx_miopen_us"] = round(big_gemm._time(lambda: torch.ops.aten.convolution_backward(
+            dyo, x, w, None, (s, s), (1, 1), (1, 1), False, [0, 0], 1, [True, False, False]), reps=10) * 1e3, 1)
+        r["dx_igemm_us"] = round(big_gemm._time(lambda: conv.conv3x3_dx(dyo, w, x.shape, stride=s), reps=10) * 1e3, 1)
+        for tw in ((64, 128) if C % 128 == 0 else (64,)):     # dx's channel tile width (the kernel picks by tile count)
+            r[f"dx_igemm_bn{tw}_us"] = round(big_gemm._time(
+                lambda: conv.conv3x3_dx(dyo, w, x.shape, stride=s, bn=tw), reps=10) * 1e3, 1)
+        stats = torch.stack([torch.zeros(C), torch.ones(C), torch.ones(C), torch.zeros(C)]).cuda()
+        slot = BwdSlot(x, stats)
+        r["dx_igemm_bnb_us"] = round(big_gemm._time(lambda: conv.conv3x3_dx(dyo, w, x.shape, bnb=slot, stride=s),
+                                                    reps=10) * 1e3, 1)
         print(json.dumps(r), flush=True)
 
 
