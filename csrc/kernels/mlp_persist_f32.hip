@@ -37,6 +37,15 @@
 //      P2 runs without a workgroup barrier: each 32-row batch chunk of the
 //          weight gradient starts as soon as the heads of its batch tiles have
 //          set their LDS flags; wave 7 signals the next step's stage with a flag.
+//      Operand preparation (one-GPU split engine, PREP in compute()): the pixel
+//          bytes become bf16 MFMA operands away from the MFMAs that use them --
+//          the step's x^T operands of P2 in the E1 window (wave 7: behind its
+//          stage DMA), the NEXT step's x operands of P0 where the staged step is
+//          read (wave 7: behind its stage DMA; the head waves: after P2, once
+//          wave 7's flag says the stage landed; the launch's first step in the
+//          prologue; a launch's last step prepares nothing).  P0 is split8 +
+//          MFMAs, and only the dz2 piece reads sit between a head flag and a
+//          chunk's MFMAs.  Same operands, same order: same bits.
 //    One LDS barrier and two inter-workgroup edges per step; the data of
 //    every edge is double-buffered by step parity and tagged with the global
 //    exchange sequence number, so buffers are never reset between launches.
@@ -224,7 +233,9 @@ struct Args {
   long long* res_ts;        // profiling only (DTF_RESIDENT_STAMPS): [run % 64][8] resident per-run stamps
   int dbg;                  // profiling only (DTF_PERSIST_DBG): bit 0 = never stage the next step's x (wrong
                             // numerics; what the per-step LDS-DMA stage costs the hand-offs), bit 1 = head
-                            // sub-phase stamps (slots 13-15, wave 0)
+                            // sub-phase stamps (slots 13-15, wave 0), bit 2 = wave 7 too prepares the next
+                            // step's operands on the late path, after P2 (same bits as its early path:
+                            // tests/test_mlp_persist_operand_prep_gpu.py)
 };
 
 // resident per-run stamp (s_memrealtime, 100 MHz) -- profiling only: 0 copier 0
@@ -806,6 +817,29 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
   constexpr int XTN = SPLIT ? 8 : NBT;
   uint32_t xf[NTW][NBT], xt[NTW][XTN];
   int lab = 0;
+  // PREP (one-GPU split engine): the byte -> bf16 conversions of both operand
+  // sets are scheduled into the hand-off waits instead of in front of the MFMAs
+  //  XF[bt]   : forward B operands of the step about to run, made from xf where the
+  //             staged step is read: wave 7 right behind its own DMA wait (early
+  //             path), a head wave after P2 (late path), the first step in the prologue
+  //  XA[k][c] : weight-gradient A operands of this step, made from xt in the E1 window
+  //  lab_n    : the next step's label until this step's head has used `lab`
+  // P0 then starts with split8 and its MFMAs, and chunk() has only the dz2 piece
+  // reads between a head flag and its MFMAs.  The head waves have no early path:
+  // the stage lands 0.8-2.8 us after their E2 publish (mid-head), never inside the
+  // E2 window, and converting in the idle polls between chunks measured slower
+  // than the late path (profiles/mlp_persist_f32_operand_prep_ab.json).
+  // (the N-GPU split kernels sit at 225-227 VGPRs: not applied there)
+  constexpr bool PREP = SPLIT && !RES && NW == 1;
+  bf16x8 XF[NBT], XA[NTW][4];
+  int lab_n = 0;
+  // an operand stays where it was made (the compiler neither sinks the
+  // conversion to its MFMA nor hoists it to where its bytes were read)
+  auto pin8 = [](bf16x8& v) {
+    u32x4 t = __builtin_bit_cast(u32x4, v);
+    asm volatile("" : "+v"(t));
+    v = __builtin_bit_cast(bf16x8, t);
+  };
   // local tile of k (an absent second tile reads local tile 0: staged, never used)
   auto tlk = [=](int k) { return k ? (tv1 ? w + 8 : 0) : w; };
   // wave 7: step st's slice -> LDS.  x rows: lane-linear [row][13 tiles] (rows of
@@ -830,13 +864,13 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
     }
     if (n0 == 0 && lane < 8) glds16(rec + XROW_BYTES + XT_BYTES + 16 * lane, smem + L_LAB);
   };
-  auto read_xf = [&]() {
+  auto read_xf = [&](int& lb) {
 #pragma unroll
     for (int k = 0; k < NTW; ++k)
 #pragma unroll
       for (int b = 0; b < NBT; ++b)
         xf[k][b] = *reinterpret_cast<const uint32_t*>(smem + L_XF + (16 * b + r) * XF_ROW + 16 * tlk(k) + 4 * g);
-    lab = smem[L_LAB + 16 * (w < NBT ? w : NBT - 1) + r];
+    lb = smem[L_LAB + 16 * (w < NBT ? w : NBT - 1) + r];
   };
   auto read_xt = [&]() {
 #pragma unroll
@@ -855,6 +889,35 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         for (int s = 0; s < NBT; ++s)
           xt[k][s] = *reinterpret_cast<const uint32_t*>(smem + L_XT + f * XTS + 16 * (s ^ ((f >> 1) & 7)) + 4 * g);
       }
+    }
+  };
+  // PREP: the staged step in LDS -> its forward operands XF and label, and its
+  // raw x^T bytes (converted one window later, when the step runs)
+  auto prep_fwd = [&](int& lb) {
+    read_xf(lb);
+#pragma unroll
+    for (int b = 0; b < NBT; ++b) XF[b] = px8(xf[0][b], xf[1][b]);
+#pragma unroll
+    for (int b = 0; b < NBT; ++b) pin8(XF[b]);
+    read_xt();
+  };
+  // PREP: this step's raw x^T bytes -> XA (wave 7, always one tile: a tile of
+  // ones in the second slot gives db1)
+  auto prep_xa = [&]() {
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int k = 0; k < NTW; ++k)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(xt[k][i]));
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) {
+        XA[0][ch] = px8(xt[0][2 * ch], xt[0][2 * ch + 1]);
+        XA[1][ch] = tv1 ? px8(xt[1][2 * ch], xt[1][2 * ch + 1]) : px8(0x01010101u, 0x01010101u);
+      }
+#pragma unroll
+      for (int k = 0; k < NTW; ++k)
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) pin8(XA[k][ch]);
     }
   };
   // Prologue, all latency overlapped (it was three serial phases, ~6 us per
@@ -946,8 +1009,10 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
   const bool l2_e1 = (*census & 1) != 0;
   const bool l2_e2 = (*census & 2) != 0;
   if (tid == 0) { PROC(c, 1); }
-  if constexpr (!RES) {
-    read_xf();
+  if constexpr (PREP) {
+    prep_fwd(lab);   // the launch's first step is prepared here
+  } else if constexpr (!RES) {
+    read_xf(lab);
     read_xt();
   }
   if (tid == 0) { PROC(c, 2); }
@@ -1001,7 +1066,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       *reinterpret_cast<u32x4*>(smem + L_LAB + 16 * tid) = v;
     }
     __syncthreads();
-    read_xf();
+    read_xf(lab);
     read_xt();
     if (c == 0 && tid == 0) { RTSC(a.run0 + st, 3); }
     const float lr_run = *reinterpret_cast<const float*>(smem + L_LAB + RES_LR_BYTE);
@@ -1072,9 +1137,12 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         for (int i = 0; i < 8; ++i) wv[i] = Wt[i >> 2][i & 3];
         bf16x8 Ah, Am, Al;
         split8(wv, Ah, Am, Al);
-        bf16x8 X[NBT];
+        bf16x8 X[NBT];   // PREP: made ahead of the step, so split8 runs straight into the MFMAs
 #pragma unroll
-        for (int b = 0; b < NBT; ++b) X[b] = px8(xf[0][b], xf[1][b]);
+        for (int b = 0; b < NBT; ++b) {
+          if constexpr (PREP) X[b] = XF[b];
+          else X[b] = px8(xf[0][b], xf[1][b]);
+        }
 #pragma unroll
         for (int b = 0; b < NBT; ++b) acc[b] = mfma16x16x32(Al, X[b], acc[b]);
 #pragma unroll
@@ -1114,8 +1182,23 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
       if (lane == 0) __hip_atomic_store(hflag + 7, st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      PH7(15);
     } else if (w == 7 && more && lane == 0) {
       __hip_atomic_store(hflag + 7, st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    // PREP: true once this wave holds the next step's operands (XF, lab_n, raw xt)
+    bool prepped = false;
+    if constexpr (PREP) {
+      if (w == 7) {
+        // wave 7 has nothing to do until the first head is done: its own operands of
+        // this step, and of the next one behind its own DMA wait
+        prep_xa();
+        if (more && !(dbg & 4)) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+          prep_fwd(lab_n);
+          prepped = true;
+        }
+      }
     }
 
     // ---------------- E1 + P1 + E2 + head (wave w < 7: batch tile w)
@@ -1130,6 +1213,9 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       const auto r1 = region_rsrc(a.xbuf + E1_OFF + (long long)(par * NJ + j) * NQ * NBT * GSLOT, NQ * NBT * GSLOT);
       put_gran(r1, (q * NBT + w) * GSLOT + 32 * lane, zs, tag, l2_e1);
       if (w == 0) { PH(3); }
+      // while the partial is in flight: this step's weight-gradient A operands
+      // (chunk() then has only the dz2 piece reads between a head flag and its MFMAs)
+      if constexpr (PREP) prep_xa();
       // this step's W2 / b1 / b2 operands of the lane, read from LDS while the
       // partial is in flight (their LDS latency off the E1 -> P1 -> E2 -> head chain)
       float w2p[4], w2d[4], b1v[4], b2v[4];
@@ -1287,11 +1373,14 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         const bf16x8 Bh = *reinterpret_cast<const bf16x8*>(bp);
         const bf16x8 Bm = *reinterpret_cast<const bf16x8*>(bp + 16 * PS);
         const bf16x8 Bl = *reinterpret_cast<const bf16x8*>(bp + 32 * PS);
-        const bf16x8 X0 = px8(xt[0][2 * ch], xt[0][2 * ch + 1]);
+        bf16x8 X0, X1;   // PREP: finished operands from the E1 window
+        if constexpr (PREP) X0 = XA[0][ch];
+        else X0 = px8(xt[0][2 * ch], xt[0][2 * ch + 1]);
         if (tv1 || w == 7) {   // wave-uniform: waves without a second tile skip its MFMAs
           // wave 7 (always one tile) multiplies a tile of ones instead: G[1] = db1
           // (lane (r, g): hidden 16j + r, every i), exact like the rest
-          const bf16x8 X1 = tv1 ? px8(xt[1][2 * ch], xt[1][2 * ch + 1]) : px8(0x01010101u, 0x01010101u);
+          if constexpr (PREP) X1 = XA[1][ch];
+          else X1 = tv1 ? px8(xt[1][2 * ch], xt[1][2 * ch + 1]) : px8(0x01010101u, 0x01010101u);
           G[0] = mfma16x16x32(X0, Bl, G[0]);
           G[1] = mfma16x16x32(X1, Bl, G[1]);
           G[0] = mfma16x16x32(X0, Bm, G[0]);
@@ -1363,7 +1452,6 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       if (lane < 16) gb = G[1][0];   // db1 of hidden 16j + lane from the ones tile
       if (lane >= 16 + NCLS) gb = 0.f;
       PH7(13);
-      PH7(15);
       if (c == 0) {   // loss / accuracy of the batch: per-row values, fixed reduction order
         const float* rl = reinterpret_cast<const float*>(smem + L_RLOSS);
         const bool hi = lane + 64 < BROWS;
@@ -1394,15 +1482,21 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       }
     }
     if (*abort_flag) { aborted = true; break; }   // final for this step: every head has reported
-    if (more) {
+    if (more && !prepped) {
       // next step's operands (this step's are consumed): x rows + label once wave 7
-      // saw the stage land, x^T
+      // saw the stage land, x^T.  PREP: the late path of the head waves, conversions
+      // included (DTF_PERSIST_DBG bit 2: wave 7 too)
       while (__hip_atomic_load(hflag + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < st + 1)
         __builtin_amdgcn_s_sleep(1);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-      read_xf();
-      read_xt();
+      if constexpr (PREP) {
+        prep_fwd(lab_n);
+      } else {
+        read_xf(lab);
+        read_xt();
+      }
     }
+    if constexpr (PREP) lab = lab_n;   // this step's head is done with its label
     if (w == 0) { PH(11); }
     if constexpr (MULTI) {
       // ---- exchange of this workgroup's gradient with the same workgroup on

@@ -3,8 +3,15 @@ from in-kernel s_memrealtime stamps (100 MHz).
 
 Stamps per step (workgroup c, wave 0, lane 0): 0 step start, 1 forward MFMAs
 done, 2 after LDS barrier A, 3 E1 published, 4 E1 flags matched, 5 z summed,
-6 E2 published, 7 E2 flags matched, 8 logits summed, 9 head done, 10 after LDS
-barrier B, 11 weight-gradient MFMAs done, 12 update done.
+6 E2 published, 7 E2 flags matched, 8 logits summed, 9 head done, 10 first
+weight-gradient chunk's heads seen done (there is no barrier B: the chunk's dz2
+piece reads and MFMAs follow), 11 weight-gradient MFMAs done (and, on the late
+path, the next step's operands read and converted), 12 update done.
+Wave 7, lane 0: 13 last head tile folded, 14 step start, 15 next step's stage
+landed in LDS (absent in a launch's last step).  The one-GPU split engine
+converts the step's weight-gradient operands inside E1_wait and, when the stage
+has landed by then, the next step's forward operands inside E2_wait
+(DTF_PERSIST_DBG=4 forces the late path after P2).
 Prints the median / p90 of every segment over steps 1..63 and all compute
 workgroups, plus per-step time and launch-level timing.
 """
@@ -22,7 +29,7 @@ from distributed_tensorflow_example_amd.data.mnist import PinnedEpoch, synthetic
 from distributed_tensorflow_example_amd.models import mlp  # noqa: E402
 
 NAMES = {"fp32": ["fwd_mfma", "barrier_A", "E1_publish", "E1_wait", "E1_load_sum", "P1_logit_publish",
-                       "E2_wait", "E2_load_sum", "head", "barrier_B", "wgrad_mfma", "update"]}
+                       "E2_wait", "E2_load_sum", "head", "head_to_first_chunk", "wgrad_mfma", "update"]}
 
 
 def main():
@@ -94,18 +101,27 @@ def main():
     out["logit_publish_skew_us_median"] = round(float(np.median(r[:, :, pub].max(1) - r[:, :, pub].min(1))), 3)
     if prec in ("fp32", "fp32-mfma"):
         # extra stamps: 13 wave 7 folded the last head tile (dW2 / db / metrics), 14 wave 7 step
-        # start, 15 wave 7 saw its next-step stage land (vmcnt(0)) -- then barrier B
+        # start, 15 wave 7 saw its next-step stage land (vmcnt(0); no stamp in the launch's last step)
         med = lambda x: round(float(np.median(x)), 3)
         rs = raw[1:G, : nj * nq, :].astype(np.float64) * 0.01
         if int(os.environ.get("DTF_PERSIST_DBG", "0")) & 2:
             out["head_detail_us_from_logits_summed"] = {
                 "softmax_done": med(rs[:, :, 13] - rs[:, :, 8]), "da_mfma_done": med(rs[:, :, 14] - rs[:, :, 8]),
                 "dz2_planes_rowsums_done": med(rs[:, :, 15] - rs[:, :, 8]), "head_done": med(rs[:, :, 9] - rs[:, :, 8])}
-        out["barrier_B_detail_us_from_w0_step_start"] = {
-            "w7_step_start": med(rs[:, :, 14] - rs[:, :, 0]), "w0_head_done": med(rs[:, :, 9] - rs[:, :, 0]),
-            "w7_last_head_folded": med(rs[:, :, 13] - rs[:, :, 0]),
-            "w7_stage_landed": med(rs[:, :, 15] - rs[:, :, 0]),
-            "barrier_B_exit": med(rs[:, :, 10] - rs[:, :, 0])}
+        else:
+            staged = rs[:-1]            # the launch's last step stages nothing
+            lead = staged[:, :, 6] - staged[:, :, 15]
+            out["wave7_detail_us_from_w0_step_start"] = {
+                "w7_step_start": med(rs[:, :, 14] - rs[:, :, 0]), "w0_head_done": med(rs[:, :, 9] - rs[:, :, 0]),
+                "w7_last_head_folded": med(rs[:, :, 13] - rs[:, :, 0]),
+                "w7_stage_landed": med(staged[:, :, 15] - staged[:, :, 0]),
+                "w0_E2_published": med(rs[:, :, 6] - rs[:, :, 0]),
+                "w0_first_chunk_start": med(rs[:, :, 10] - rs[:, :, 0])}
+            # the early operand preparation needs the stage in LDS when a head wave has
+            # published its logits (stamp 6): lead > 0 means it had landed
+            out["stage_landed_before_E2_publish_us"] = {
+                "median": med(lead), "min": round(float(lead.min()), 3),
+                "fraction_landed": round(float((lead > 0).mean()), 4)}
     late = (r[:, :, 0] - r[:, :, 0].min(axis=1, keepdims=True)).mean(axis=0)
     out["step_start_lateness_us_by_wg"] = np.round(late, 2).tolist()
     np.save(os.path.join(REPO, "gpurun_out", f"phase_raw_{prec}.npy"), raw[:G])
