@@ -446,6 +446,75 @@ void graph_mlp_step(at::Tensor x, at::Tensor ylab, at::Tensor W1, at::Tensor b1,
   hip_check(dtfk_graph_mlp_step(&p, cur_stream()), "graph_mlp_step");
 }
 
+// Forward-only evaluation of N rows (csrc/kernels/mlp_eval.hip): loss sum,
+// correct count and rows accumulated into `out` (int64[3] holding a
+// dtfk::mlpe::Record: [0] is the fp64 loss sum's bits), started over when
+// `reset`.  x: fp32 or uint8 [N, K]; labels: uint8 / int32 class ids [N] or an
+// fp32 one-hot [N, C]; the parameters are any four fp32 tensors (slices of a
+// flat master or separate variables).  Optional pred int32 [N], logits fp32 [N, C].
+void mlp_eval(at::Tensor x, at::Tensor labels, at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2, int act,
+              bool naive, at::Tensor out, bool reset, c10::optional<at::Tensor> pred,
+              c10::optional<at::Tensor> logits) {
+  for (const at::Tensor* t : {&W1, &b1, &W2, &b2}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
+                "mlp_eval: fp32 contiguous device parameters expected");
+  }
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
+                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kByte),
+              "mlp_eval: x must be a contiguous 2-D fp32 or uint8 device tensor");
+  TORCH_CHECK(W1.dim() == 2 && W2.dim() == 2, "mlp_eval: 2-D W1, W2");
+  const int64_t N = x.size(0), K = x.size(1), H = W1.size(1), C = W2.size(1);
+  TORCH_CHECK(N >= 1 && N <= INT32_MAX, "mlp_eval: N >= 1 rows expected, got ", N);
+  TORCH_CHECK(W1.size(0) == K && W2.size(0) == H && b1.numel() == H && b2.numel() == C, "mlp_eval: shape mismatch");
+  TORCH_CHECK(K >= 1 && K <= INT32_MAX && H >= 1 && H <= 128 && C >= 1 && C <= 16,
+              "mlp_eval: shapes outside the kernel's gate (K >= 1, H <= 128, C <= 16)");
+  TORCH_CHECK(act == 0 || act == 1, "mlp_eval: act must be 0 (sigmoid) or 1 (relu)");
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous(), "mlp_eval: labels must be a contiguous device tensor");
+  dtfk::mlpe::Eval p{};
+  if (labels.scalar_type() == at::kFloat) {
+    TORCH_CHECK(labels.dim() == 2 && labels.size(0) == N && labels.size(1) == C,
+                "mlp_eval: one-hot labels must be fp32 [N, C]");
+    p.label_kind = 2;
+  } else {
+    TORCH_CHECK((labels.scalar_type() == at::kByte || labels.scalar_type() == at::kInt) && labels.numel() == N,
+                "mlp_eval: class ids must be uint8 or int32 [N]");
+    p.label_kind = labels.scalar_type() == at::kByte ? 0 : 1;
+  }
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.scalar_type() == at::kLong && out.numel() >= 3,
+              "mlp_eval: out must be an int64[3] device tensor");
+  if (x.scalar_type() == at::kByte) {
+    TORCH_CHECK(K % 4 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 4 == 0,
+                "mlp_eval: uint8 x needs K % 4 == 0 and 4-byte aligned rows");
+    p.xu = x.data_ptr<uint8_t>();
+  } else {
+    p.x = x.data_ptr<float>();
+  }
+  if (pred.has_value()) {
+    TORCH_CHECK(pred->is_cuda() && pred->is_contiguous() && pred->scalar_type() == at::kInt && pred->numel() == N,
+                "mlp_eval: pred must be an int32 [N] device tensor");
+    p.pred = pred->data_ptr<int>();
+  }
+  if (logits.has_value()) {
+    TORCH_CHECK(logits->is_cuda() && logits->is_contiguous() && logits->scalar_type() == at::kFloat &&
+                    logits->numel() == N * C,
+                "mlp_eval: logits must be an fp32 [N, C] device tensor");
+    p.logits = logits->data_ptr<float>();
+  }
+  // per-tile {loss, correct} (scratch from the caching allocator, this stream's)
+  at::Tensor part = at::empty({dtfk_mlp_eval_part_words(N)}, W1.options());
+  p.labels = labels.data_ptr();
+  p.W1 = W1.data_ptr<float>();
+  p.b1 = b1.data_ptr<float>();
+  p.W2 = W2.data_ptr<float>();
+  p.b2 = b2.data_ptr<float>();
+  p.part = part.data_ptr<float>();
+  p.rec = reinterpret_cast<dtfk::mlpe::Record*>(out.data_ptr<int64_t>());
+  p.reset = reset ? 1 : 0;
+  p.N = (int)N, p.K = (int)K, p.H = (int)H, p.C = (int)C;
+  p.act = act, p.naive = naive ? 1 : 0;
+  hip_check(dtfk_mlp_eval(&p, cur_stream()), "mlp_eval");
+}
+
 // The lowered Session.run of the reference's training graph as ONE host call
 // (compat/lowering.py, in-kernel SGD): the numpy feeds x [B,K] / y_ [B,C] and the
 // learning rate go into a pinned staging slot (one memcpy, GIL released), ONE
@@ -999,6 +1068,9 @@ void init_mlp(py::module& m) {
   m.def("graph_mlp_step", &graph_mlp_step, py::arg("x"), py::arg("ylab"), py::arg("W1"), py::arg("b1"),
         py::arg("W2"), py::arg("b2"), py::arg("a2buf"), py::arg("dz2buf"), py::arg("grads"), py::arg("metrics"),
         py::arg("gstep"), py::arg("lr"), py::arg("act"), py::arg("naive"), py::arg("sgd"));
+  m.def("mlp_eval", &mlp_eval, py::arg("x"), py::arg("labels"), py::arg("W1"), py::arg("b1"), py::arg("W2"),
+        py::arg("b2"), py::arg("act"), py::arg("naive"), py::arg("out"), py::arg("reset"),
+        py::arg("pred") = py::none(), py::arg("logits") = py::none());
   py::class_<PersistF32Plan>(m, "PersistF32Plan")
       .def(py::init<at::Tensor, at::Tensor, int64_t, int, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, double, int, int, at::Tensor, at::Tensor, int64_t, int, int,

@@ -1,5 +1,5 @@
 // The host entry points of the MLP kernel files (mlp_step.hip, mlp_gemm.hip,
-// mlp_persist_f32.hip, graph_mlp.hip), declared once: csrc/bind_mlp.cpp calls
+// mlp_persist_f32.hip, graph_mlp.hip, mlp_eval.hip), declared once: csrc/bind_mlp.cpp calls
 // through these declarations and every defining file includes them, so a
 // definition that disagrees with its declaration does not compile.  Host-only:
 // no device code here.
@@ -88,6 +88,37 @@ struct Step {
 };
 
 }  // namespace gmlp
+
+namespace mlpe {
+
+// What an evaluation accumulates on the device (mlp_eval.hip): 24 bytes, 8-byte aligned.
+struct Record {
+  double loss_sum;          // sum of the per-row losses
+  long long correct;        // rows whose argmax(z3) is the label
+  long long rows;
+};
+
+// One forward-only evaluation of N rows (mlp_eval.hip).  Value-initialise it
+// (`Eval p{}`) and set what the call needs; everything else stays null / zero.
+struct Eval {
+  const float* x;           // rows [N][K] fp32 ...
+  const uint8_t* xu;        //   ... or uint8 pixels instead (K % 4 == 0, 4-byte aligned); exactly one is non-null
+  const void* labels;       // label_kind 0: uint8 class ids [N], 1: int32 ids [N], 2: fp32 one-hot [N][C]
+  int label_kind;
+  const float* W1;          // [K][H], [H], [H][C], [C]: the flat master's slices or the Session's variables
+  const float* b1;
+  const float* W2;
+  const float* b2;
+  float* part;              // scratch of dtfk_mlp_eval_part_words(N) 4-byte words
+  Record* rec;              // accumulated into; reset != 0: started over by this call
+  int reset;
+  int* pred;                // optional [N] argmax(z3)
+  float* logits;            // optional [N][C] z3
+  int N, K, H, C;           // N >= 1, K >= 1, H <= 128, C <= 16
+  int act, naive;           // act 0 sigmoid, 1 relu; naive: loss as -sum(y_ log softmax), else the stable form
+};
+
+}  // namespace mlpe
 }  // namespace dtfk
 
 extern "C" {
@@ -134,4 +165,7 @@ hipError_t dtfk_mlp_persist_f32_launch(const dtfk::mlpf::Launch* p, hipStream_t 
 // ---- graph_mlp.hip
 long long dtfk_graph_mlp_part_floats(int B, int H);
 hipError_t dtfk_graph_mlp_step(const dtfk::gmlp::Step* p, hipStream_t stream);
+// ---- mlp_eval.hip
+long long dtfk_mlp_eval_part_words(long long N);
+hipError_t dtfk_mlp_eval(const dtfk::mlpe::Eval* p, hipStream_t stream);
 }

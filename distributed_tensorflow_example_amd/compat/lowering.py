@@ -34,6 +34,17 @@ accuracy of the run (pre-update, as TF evaluates them in the same run) are
 seeded into the run's memo, so summaries / cost fetches of the same run cost
 no extra kernels.
 
+A run that fetches NO train op but only that graph's loss and / or accuracy
+with x and y_ fed as NumPy arrays -- the reference's closing
+`sess.run(accuracy, feed_dict={x: mnist.test.images, y_: mnist.test.labels})`
+(example.py:187) -- is the forward-only evaluation of models/mlp.py
+`evaluate` on the graph's variables (csrc/kernels/mlp_eval.hip: the feed
+copied in chunks on a side stream, accumulated on the device, one
+read-back) instead of ~25 eager ops on a 31 MB feed; a loader
+`PixelBatch` ships its uint8 source.  It is local to the worker (no
+collective) and known once the graph's train op has been lowered
+(`MLPStepPlan.eval_runs` counts them).
+
 and lr2.py's sparse logistic regression (lr2.py:359-396) over a partitioned
 (ps-placed, row-sharded) W:
 
@@ -66,6 +77,7 @@ import torch
 from .graph import Operation, Tensor
 
 _CACHE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()   # train_op -> plan | False
+_EVAL: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()    # loss / accuracy node -> weakref(MLPStepPlan)
 
 
 _MODS = {}
@@ -253,6 +265,10 @@ class MLPStepPlan(_PlanBase):
         self.steps = 0
         self._rplan = None           # compat/resident.py handle (one worker, uint8 loader batches)
         self.resident_steps = 0
+        self.eval_runs = 0           # lowered runs that fetched only the loss / accuracy (run_eval)
+        for node in (pat.loss, self.accuracy):
+            if node is not None:
+                _EVAL[node] = weakref.ref(self)
 
     # -------------------------------------------------------------- feeds
     @staticmethod
@@ -402,6 +418,37 @@ class MLPStepPlan(_PlanBase):
         else:
             self._seed(ctx.memo, self.metrics)
         self.steps += 1
+        return True
+
+    def run_eval(self, ctx) -> bool:
+        """A run that fetches only this graph's loss / accuracy (no train op), x
+        and y_ fed as NumPy arrays: models/mlp.py `evaluate` on the variables
+        (csrc/kernels/mlp_eval.hip), the two values seeded as the NumPy float32
+        scalars the eager path returns.  False: not applicable, nothing done."""
+        pat = self.pat
+        W1, b1, W2, b2 = pat.W1.value, pat.b1.value, pat.W2.value, pat.b2.value
+        if not all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32
+                   for v in (W1, b1, W2, b2)):
+            return False
+        K, H, C = W1.shape[0], W1.shape[1], W2.shape[1]
+        if not (K >= 1 and 1 <= H <= 128 and 1 <= C <= 16):      # the kernel's shape gate
+            return False
+        fx, fy = self._feed_of(ctx, pat.x), self._feed_of(ctx, pat.ylab)
+        if fx is None or fy is None or fx.ndim != 2 or fx.shape[0] < 1 or fx.shape[1] != K \
+                or fy.shape != (fx.shape[0], C):
+            return False
+        u8 = getattr(fx, "u8", None)
+        if u8 is not None and not fx.flags.writeable and u8.shape == fx.shape and u8.dtype == np.uint8 \
+                and K % 4 == 0:
+            fx = u8                     # data/mnist.py PixelBatch: ship the uint8 source (bit-identical)
+        _resident_mod().quiesce_all()   # a resident engine holds the variables in registers
+        from ..models import mlp
+        loss, acc = mlp.evaluate((W1.data, b1.data, W2.data, b2.data), fx, fy,
+                                 act="sigmoid" if pat.act == 0 else "relu", naive=bool(pat.naive))
+        ctx.memo[id(pat.loss)] = np.float32(loss)
+        if self.accuracy is not None:
+            ctx.memo[id(self.accuracy)] = np.float32(acc)
+        self.eval_runs += 1
         return True
 
     def _run_native_plan(self, ctx, flat, W1, b1, W2, b2) -> bool:
@@ -904,6 +951,23 @@ def _flatten(f, out: List[Any]):
     return out
 
 
+def _try_lower_eval(ctx, flat) -> None:
+    """No train op fetched: if every fetch is ONE lowered plan's loss or
+    accuracy node, run its forward-only evaluation (MLPStepPlan.run_eval)."""
+    plan = None
+    for f in flat:
+        try:
+            ref = _EVAL.get(f)
+        except TypeError:               # a fetch by name, a callable: not ours
+            return
+        p = ref() if ref is not None else None
+        if p is None or (plan is not None and p is not plan):
+            return
+        plan = p
+    if plan is not None:
+        plan.run_eval(ctx)
+
+
 def try_lower(session, fetches, ctx, flat=None) -> None:
     """Run lowered plans for train ops in `fetches`, seeding ctx.memo."""
     lower = getattr(session, "_lower", None)          # read once per Session (compat/session.py)
@@ -911,6 +975,9 @@ def try_lower(session, fetches, ctx, flat=None) -> None:
         return
     if flat is None:
         flat = _flatten(fetches, [])
+    if _EVAL and not any(getattr(f, "_lowering", None) is not None for f in flat):
+        _try_lower_eval(ctx, flat)
+        return
     for f in flat:
         if getattr(f, "_lowering", None) is None or not isinstance(f, Operation):
             continue

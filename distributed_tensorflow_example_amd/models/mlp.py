@@ -2,7 +2,7 @@
 (example.py:69-128; sigmoid hidden layer, softmax output, mean cross-entropy,
 GradientDescentOptimizer(0.0005), batch 100 per worker).
 
-Three implementations of the same step:
+Three implementations of the same step, and one evaluation:
 
 * `reference_step`   -- plain PyTorch fp32 (the numerics oracle for the HIP
                         kernels, and the CPU/gloo path of BASELINE config #1).
@@ -14,6 +14,15 @@ Three implementations of the same step:
                         in sync data parallel (csrc/kernels/mlp_step.hip),
                         replayed from hipGraphs by `MLPStepRunner` with the
                         input streamed from pinned host memory on a side stream.
+* `evaluate`         -- held-out loss / accuracy (example.py:187), forward only:
+                        the exact-fp32 MFMA kernel of csrc/kernels/mlp_eval.hip
+                        over uint8 or float rows, ids or one-hot labels, on a
+                        flat master or four separate tensors; host arrays are
+                        copied chunk by chunk on a side stream under the
+                        previous chunk's kernel and accumulated on the device
+                        (one read-back).  Also
+                        `FusedMLPTrainer.evaluate` / `GemmMLPTrainer.evaluate`
+                        on the trainer's own master.  CPU parameters: PyTorch.
 
 Parameter layout (flat fp32, TF variable order and names):
   weights/Variable [784,100], weights/Variable_1 [100,10],
@@ -93,6 +102,164 @@ def reference_step(flat: torch.Tensor, x: torch.Tensor, labels: torch.Tensor, lr
     loss, acc, g = reference_loss_and_grad(flat, x, labels, act)
     flat.sub_(lr * g)
     return loss, acc
+
+
+def _eval_params(params):
+    """(W1, b1, W2, b2) of a flat tensor in this module's layout or of the four tensors."""
+    if isinstance(params, torch.Tensor):
+        if params.dim() != 1 or params.numel() != NPARAM:
+            raise ValueError(f"flat parameters must have {NPARAM} elements")
+        p = unflatten(params.detach())
+        return (p["weights/Variable"], p["biases/Variable"], p["weights/Variable_1"], p["biases/Variable_1"])
+    W1, b1, W2, b2 = (t.detach() for t in params)
+    return W1, b1, W2, b2
+
+
+def _eval_labels(labels):
+    """Labels as the kernel takes them: uint8 / int32 ids [N] or a float32 one-hot [N, C]."""
+    if isinstance(labels, torch.Tensor):
+        if labels.dim() == 2 and labels.dtype == torch.float32:
+            return labels
+        if labels.dim() != 1 or labels.is_floating_point():
+            raise ValueError("labels must be integer class ids [N] or a float32 one-hot [N, C]")
+        return labels if labels.dtype in (torch.uint8, torch.int32) else labels.to(torch.int32)
+    labels = np.asarray(labels)
+    if labels.ndim == 2 and labels.dtype == np.float32:
+        return labels
+    if labels.ndim != 1 or labels.dtype.kind not in "iu":
+        raise ValueError("labels must be integer class ids [N] or a float32 one-hot [N, C]")
+    return labels if labels.dtype in (np.uint8, np.int32) else labels.astype(np.int32)
+
+
+def _evaluate_cpu(W1, b1, W2, b2, x, labels, act, naive, return_predictions):
+    """The same quantities with PyTorch fp32 on the host (gloo / CPU path)."""
+    x = torch.as_tensor(x)
+    labels = torch.as_tensor(labels)
+    xf = x.to(torch.float32) / 255.0 if x.dtype == torch.uint8 else x.to(torch.float32)
+    z3 = _act(xf @ W1 + b1, act) @ W2 + b2
+    y = labels if labels.dim() == 2 else torch.nn.functional.one_hot(labels.long(), W2.shape[1]).float()
+    ids = labels.argmax(1) if labels.dim() == 2 else labels.long()
+    if naive:
+        rows = -torch.sum(y * torch.log(torch.softmax(z3, 1)), 1)
+    else:
+        rows = -torch.sum(y * torch.log_softmax(z3, 1), 1)
+    pred = z3.argmax(1)
+    loss = float(rows.double().sum()) / x.shape[0]
+    acc = int((pred == ids).sum()) / x.shape[0]
+    return (loss, acc, pred.to(torch.int32)) if return_predictions else (loss, acc)
+
+
+def _host_tensor(a: np.ndarray) -> torch.Tensor:
+    """A tensor view of a host array that is only read (a read-only array is fine)."""
+    import warnings
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return torch.from_numpy(a)
+
+
+_EVAL_STAGE = {}     # device -> two device staging slots (grown on demand), their events, the side stream
+
+
+def _eval_stage(dev, xbytes, lbytes):
+    st = _EVAL_STAGE.get(dev)
+    if st is None or st["xcap"] < xbytes or st["lcap"] < lbytes:
+        xcap = max(xbytes, st["xcap"] if st else 0)
+        lcap = max(lbytes, st["lcap"] if st else 0)
+        st = _EVAL_STAGE[dev] = dict(
+            xcap=xcap, lcap=lcap,
+            dx=[torch.empty(xcap, dtype=torch.uint8, device=dev) for _ in range(2)],
+            dl=[torch.empty(lcap, dtype=torch.uint8, device=dev) for _ in range(2)],
+            used=[None, None], side=st["side"] if st else torch.cuda.Stream(device=dev))
+    return st
+
+
+def evaluate(params, x, labels, act: str = "sigmoid", naive: bool = False, chunk_rows: int = 16384,
+             return_predictions: bool = False):
+    """Mean loss and accuracy of the model on held-out rows, forward only
+    (example.py:187).  Returns `(loss, accuracy)` as Python floats, and the int32
+    predictions (argmax of the logits, first maximum on ties) as well with
+    `return_predictions`.
+
+    params: the flat tensor of this module's layout, or the four tensors
+        (W1 [K, H], b1 [H], W2 [H, C], b2 [C]).
+    x: [N, K] uint8 pixels (evaluated as x / 255, bit-identical to the loader's
+        float32 array) or float32; a device tensor or a NumPy array.
+    labels: class ids [N] or a float32 one-hot [N, C]; device tensor or NumPy.
+    naive: the loss as -sum(y_ log softmax) (example.py:103), else the stable form.
+
+    GPU parameters run csrc/kernels/mlp_eval.hip on the current stream, behind
+    the work already queued there.  Host arrays go to two device staging
+    buffers on a side stream, `chunk_rows` rows at a time, so device memory
+    stays bounded for any N: the copy of chunk i + 1 overlaps the kernel of
+    chunk i (events order the two streams), the kernel accumulates into a
+    device record and ONE device-to-host copy fetches it at the end.  The
+    copies read the caller's arrays in place: a pinned staging copy in front of
+    them cost more than it saved (10,000 x 784 float32: 1.3-1.4 ms against
+    0.74-0.83 ms, the single-threaded host copy being slower than the
+    transfer; profiles/mlp_eval_ab.json).  CPU parameters compute the same
+    quantities with PyTorch."""
+    W1, b1, W2, b2 = _eval_params(params)
+    if x.ndim != 2:
+        raise ValueError("x must be [N, K]")
+    N, K = int(x.shape[0]), int(x.shape[1])
+    if N == 0:
+        raise ValueError("evaluate needs at least one row")
+    labels = _eval_labels(labels)
+    if labels.shape[0] != N:
+        raise ValueError("x and labels differ in rows")
+    if not W1.is_cuda:
+        return _evaluate_cpu(W1, b1, W2, b2, x, labels, act, naive, return_predictions)
+    C_ = _native.load()
+    dev = W1.device
+    args = (W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous(), ACTS[act], bool(naive))
+    with torch.cuda.device(dev):
+        rec = torch.empty(3, dtype=torch.int64, device=dev)
+        pred = torch.empty(N, dtype=torch.int32, device=dev) if return_predictions else None
+        x_host, l_host = not isinstance(x, torch.Tensor), not isinstance(labels, torch.Tensor)
+        if x_host:
+            x = np.ascontiguousarray(x if x.dtype in (np.uint8, np.float32) else x.astype(np.float32))
+        elif x.dtype not in (torch.uint8, torch.float32):
+            x = x.float()
+        if l_host:
+            labels = np.ascontiguousarray(labels)
+        if not (x_host and l_host):
+            xd = torch.tensor(x, device=dev) if x_host else x.to(dev).contiguous()
+            ld = torch.tensor(labels, device=dev) if l_host else labels.to(dev).contiguous()
+            C_.mlp_eval(xd, ld, *args, rec, True, pred, None)
+        else:
+            R = min(int(chunk_rows), N)
+            if R < 1:
+                raise ValueError("chunk_rows must be positive")
+            xrow, lrow = K * x.itemsize, labels[0].size * labels.itemsize    # bytes per row (C-contiguous)
+            st = _eval_stage(dev, R * xrow, R * lrow)
+            main, side = torch.cuda.current_stream(), st["side"]
+            side.wait_stream(main)      # (a freshly allocated slot may be memory the queued work still uses)
+            xdt = torch.uint8 if x.dtype == np.uint8 else torch.float32
+            ldt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32,
+                   np.dtype(np.float32): torch.float32}[labels.dtype]
+            xb = _host_tensor(np.asarray(x).reshape(-1).view(np.uint8))
+            lb = _host_tensor(np.asarray(labels).reshape(-1).view(np.uint8))
+            for i, r0 in enumerate(range(0, N, R)):
+                n = min(R, N - r0)
+                s = i % 2
+                with torch.cuda.stream(side):
+                    if st["used"][s] is not None:
+                        side.wait_event(st["used"][s])      # the kernel that last read this device slot is done
+                    st["dx"][s][:n * xrow].copy_(xb[r0 * xrow:(r0 + n) * xrow], non_blocking=True)
+                    st["dl"][s][:n * lrow].copy_(lb[r0 * lrow:(r0 + n) * lrow], non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record(side)
+                main.wait_event(copied)
+                xd = st["dx"][s][:n * xrow].view(xdt).view(n, K)
+                ld = st["dl"][s][:n * lrow].view(ldt).view((n,) + tuple(labels.shape[1:]))
+                C_.mlp_eval(xd, ld, *args, rec, i == 0, None if pred is None else pred[r0:r0 + n], None)
+                st["used"][s] = torch.cuda.Event()
+                st["used"][s].record(main)
+        r = rec.cpu()                                    # the one read-back: {loss sum (fp64), correct, rows}
+    loss = float(r.view(torch.float64)[0]) / int(r[2])
+    acc = int(r[1]) / int(r[2])
+    return (loss, acc, pred) if return_predictions else (loss, acc)
 
 
 class MLP(torch.nn.Module):
@@ -296,6 +463,13 @@ class FusedMLPTrainer:
         kind = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}[x.dtype]
         self.enqueue_step(x.contiguous(), 0, kind, labels.to(torch.uint8).contiguous(), 0)
 
+    def evaluate(self, x, labels, **kw):
+        """`evaluate` on this trainer's fp32 master with its activation and loss
+        form, on the current stream behind the steps already queued (a call after
+        `PersistentMLPRunner.run` sees the trained parameters).  Changes nothing:
+        parameters, global_step and the metrics ring stay as they are."""
+        return evaluate(self.params, x, labels, act=self.act_name, naive=self.naive, **kw)
+
 
 class GemmMLPTrainer:
     """Large-batch step of the same model (csrc/kernels/mlp_gemm.hip), 4
@@ -408,6 +582,10 @@ class GemmMLPTrainer:
         if x.dtype != torch.uint8:
             raise ValueError("GemmMLPTrainer.step_tensors takes uint8 pixels")
         self.enqueue_step(x.contiguous().view(-1), 0, 0, labels.to(torch.uint8).contiguous(), 0)
+
+    def evaluate(self, x, labels, **kw):
+        """`evaluate` on this trainer's fp32 master (see `FusedMLPTrainer.evaluate`)."""
+        return evaluate(self.params, x, labels, act=self.act_name, naive=self.naive, **kw)
 
 
 class MLPStepRunner:

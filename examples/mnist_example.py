@@ -186,6 +186,7 @@ def run_graph_worker(server, mnist, logs_path):
             np.savez(os.path.join(FLAGS.dump_dir, f"worker_{FLAGS.task_index}.npz"), **dump)
             with open(os.path.join(FLAGS.dump_dir, f"worker_{FLAGS.task_index}.json"), "w") as f:
                 json.dump({"lowered_steps": getattr(plan, "steps", 0) if plan else 0,
+                           "eval_runs": getattr(plan, "eval_runs", 0) if plan else 0,
                            "native_plan_steps": int(cplan.steps()) if cplan is not None else 0,
                            "native_plan_ipc": bool(cplan.has_ipc()) if cplan is not None else False,
                            "rccl_comm": w is not None and w.comm is not None,
@@ -228,8 +229,7 @@ def run_fused_worker(server, mnist):
         if FLAGS.max_steps and steps >= FLAGS.max_steps:
             break
     p = mlp.unflatten(tr.get_params().cpu())
-    z = mlp.reference_forward(tr.get_params().cpu(), torch.from_numpy(mnist.test.images), FLAGS.activation)
-    acc = float((z.argmax(1).numpy() == mnist.test.labels.argmax(1)).mean())
+    _, acc = tr.evaluate(mnist.test.images_u8, mnist.test.labels_u8)    # on the GPU (csrc/kernels/mlp_eval.hip)
     params = [p[k].numpy() for k in ("weights/Variable", "weights/Variable_1", "biases/Variable",
                                      "biases/Variable_1")]
     server.signal_done()
@@ -272,8 +272,7 @@ def run_persistent_worker(server, mnist, tr):
                       flush=True)
         loss = float(m[-1][0])
         steps += n
-    z = mlp.reference_forward(tr.get_params().cpu(), torch.from_numpy(mnist.test.images), FLAGS.activation)
-    acc = float((z.argmax(1).numpy() == mnist.test.labels.argmax(1)).mean())
+    _, acc = tr.evaluate(mnist.test.images_u8, mnist.test.labels_u8)    # on the GPU (csrc/kernels/mlp_eval.hip)
     p = mlp.unflatten(tr.get_params().cpu())
     params = [p[k].numpy() for k in ("weights/Variable", "weights/Variable_1", "biases/Variable",
                                      "biases/Variable_1")]
