@@ -29,8 +29,9 @@
 //          block; logits = b2 + sum_j (block order) -> identical in all 28.
 //          softmax / cross-entropy / argmax, dz3, da2 = W2 dz3 (4 MFMAs),
 //          dz2 = da2 * act' -> LDS.
-//      P2  dW1 tiles = x^T dz2 over the batch (28 MFMAs per tile, x^T bytes from
-//          the feature-major stage copy), W1 -= lr/(255 B) dW1 in registers;
+//      P2  dW1 tiles = x^T dz2 over the batch (28 MFMAs per tile, x^T bytes by
+//          transposing LDS reads of the same row-major image the forward
+//          reads: ds_read_b64_tr_b8), W1 -= lr/(255 B) dW1 in registers;
 //          wave 7 also: dW2 (28 MFMAs), db1, db2, metrics, update of the LDS
 //          copies of W2[block j], b1[block j], b2 -- identical in every
 //          workgroup that holds them (same inputs, same order).
@@ -52,8 +53,15 @@
 //  * x enters the MFMAs as exact integers 0..255 (v_cvt_f32_ubyte); the 1/255
 //    pixel scale and the 1/B loss mean are applied to the fp32 sums.
 //  * 16 COPIER workgroups pull chunk c+1 from pinned host memory over PCIe into
-//    the other device stage (row-major x, feature-major x^T, labels) while the
-//    compute workgroups run chunk c.
+//    the other device stage (a record per step: row-major x [112][784] u8, rows
+//    >= B zero, then 128 label bytes; 87,936 B) while the compute workgroups run
+//    chunk c.
+//  * wave 7 stages ONE image per step (the slice's 112 rows x 208 B, + labels)
+//    with LDS-DMA while the gathers poll: half the bytes of the row-major +
+//    feature-major pair it replaced, 6.84 -> 6.64 us/step.  Dense (planar) granule
+//    slots with padding lanes masked out of both edges measured 2 % SLOWER than
+//    the interleaved slots below, alone and on top of this, and are not in
+//    (profiles/mlp_persist_f32_handoff_bytes_ab.json).
 //  * N GPUs (MULTI, NW = the peer-table width W is unrolled for: 2, 4, 8):
 //    after P2 every compute workgroup exchanges its gradient (its dW1 tiles +
 //    the block's small gradients) with the same workgroup on every peer through
@@ -101,7 +109,7 @@ constexpr int NQ = 4;              // feature slices: 13, 12, 12, 12 tiles of 16
 constexpr int NTW = 2;             // feature tiles per wave (local tiles w and w + 8)
 constexpr int NBT = 7;             // batch tiles of 16 (B <= 112)
 constexpr int BROWS = 16 * NBT;    // 112
-constexpr int XTS = 128;           // x^T row stride (batch padded)
+constexpr int XTS = 128;           // batch rows padded to the weight gradient's K (4 chunks of 32)
 constexpr int NCOMP = NJ * NQ;     // 28 compute workgroups: one XCD
 constexpr int THREADS = 512;
 constexpr int NCOP = 16;           // copier workgroups
@@ -114,9 +122,10 @@ __host__ __device__ constexpr int ntile(int q) { return q == 0 ? 13 : 12; }
 constexpr int OFF_W2 = 78400, OFF_B1 = 79400, OFF_B2 = 79500;
 
 // device stage record of one step
+// (no feature-major copy: the weight gradient's x^T fragments are transposing LDS
+// reads of the row-major image, see read_xt)
 constexpr long long XROW_BYTES = (long long)BROWS * DIN;   // [112][784] u8, rows >= B zero
-constexpr long long XT_BYTES = (long long)DIN * XTS;       // [784][128] u8, batch >= B zero
-constexpr long long REC = XROW_BYTES + XT_BYTES + 128;     // + labels [128]
+constexpr long long REC = XROW_BYTES + 128;                // + labels [128]
 
 // exchange buffer (bytes): every payload float travels as an 8-byte granule
 // {value, tag} (the data is the flag: no separate flag word, no drain before a
@@ -161,19 +170,17 @@ constexpr int L_FLAG = L_RMET + 64;
 // with LDS-DMA (global_load_lds_dwordx4, lane-linear 1 KiB pieces) instead of
 // fragment-shaped global loads in every wave (16 cache lines per instruction:
 // those loads were TA-bound, ~2.5 us of every step)
-constexpr int XF_ROW = 13 * 16;                        // [112 rows][13 tiles x 16 features] u8
-constexpr int L_XF = L_FLAG + 64;
-constexpr int XF_CHUNKS = BROWS * 13;                  // 1456 x 16 B
-constexpr int L_XT = L_XF + BROWS * XF_ROW;            // [208 features][128 batch] u8, 16-B chunks XOR-swizzled
-constexpr int XT_CHUNKS = 13 * 16 * 8;                 // 1664 x 16 B
-constexpr int L_LAB = L_XT + 13 * 16 * XTS;            // [128] labels
+constexpr int XF_ROW = 13 * 16;                        // [128 rows][13 tiles x 16 features] u8: rows < 112 staged,
+constexpr int L_XF = L_FLAG + 64;                      // rows 112..127 zeroed once per launch (the weight
+constexpr int XF_CHUNKS = BROWS * 13;                  // gradient's K = 128 batch rows); 1456 x 16 B staged
+constexpr int L_LAB = L_XF + XTS * XF_ROW;             // [128] labels
 constexpr int PS = XTS + 8;                            // split mode: bf16 plane row stride (elements)
 constexpr int L_DZP = L_LAB + 128;                     // split mode: [3 pieces][16 hidden][PS] dz2 bf16
 constexpr int L_HFLAG = L_DZP + 3 * 16 * PS * 2;       // [8] head-done flags (step + 1) of waves 0..6
 constexpr int L_DW2P = L_HFLAG + 64;                   // [7 batch tiles][64 lanes] f32x4 dW2 partials
 constexpr int L_RLOSS = L_DW2P + NBT * 64 * 16;        // [2][128] per-row loss / correct of the step
 constexpr int LDS_COMPUTE = L_RLOSS + 2 * 128 * 4;
-static_assert(L_XF % 1024 == 0 && L_XT % 16 == 0 && L_LAB % 16 == 0, "LDS-DMA bases");
+static_assert(L_XF % 1024 == 0 && L_LAB % 16 == 0, "LDS-DMA bases");
 static_assert(L_DW2P % 16 == 0, "dW2 partials: 16-B lanes");
 constexpr int CROW = DIN + 16;                         // copier LDS row stride (800)
 constexpr int LDS_COPIER = BROWS * CROW;               // 89600
@@ -521,8 +528,8 @@ __device__ __forceinline__ void sum_small(const PeerRs<NW>& prs, int W, int rank
 
 // ------------------------------------------------------------------ copier
 // task = one step of the next chunk: 112 rows of 784 pixels from the pinned host
-// record into LDS (rows >= B zero), then the row-major image, the feature-major
-// copy (4x4 byte transposes with v_perm) and the labels into the device stage.
+// record into LDS (rows >= B zero), then the row-major image and the labels
+// into the device stage.
 __device__ void copier(const Args& a, int cid, uint8_t* smem) {
   const int tid = threadIdx.x;
   const int B = a.B;
@@ -537,30 +544,11 @@ __device__ void copier(const Args& a, int cid, uint8_t* smem) {
       if (row < B) v = reinterpret_cast<const uint4*>(src)[row * C16 + c];
       *reinterpret_cast<uint4*>(smem + row * CROW + 16 * c) = v;
     }
-    if (tid < 128) dst[XROW_BYTES + XT_BYTES + tid] = tid < B ? src[(long long)B * DIN + tid] : (uint8_t)0;
+    if (tid < 128) dst[XROW_BYTES + tid] = tid < B ? src[(long long)B * DIN + tid] : (uint8_t)0;
     __syncthreads();
     for (int k = tid; k < BROWS * C16; k += THREADS) {
       const int row = k / C16, c = k % C16;
       reinterpret_cast<uint4*>(dst)[row * C16 + c] = *reinterpret_cast<const uint4*>(smem + row * CROW + 16 * c);
-    }
-    uint8_t* xt = dst + XROW_BYTES;
-    for (int k = tid; k < (DIN / 4) * (BROWS / 4); k += THREADS) {
-      const int fq = k / (BROWS / 4), rq = k % (BROWS / 4);
-      const uint8_t* p = smem + 4 * rq * CROW + 4 * fq;
-      const uint32_t r0 = *reinterpret_cast<const uint32_t*>(p);
-      const uint32_t r1 = *reinterpret_cast<const uint32_t*>(p + CROW);
-      const uint32_t r2 = *reinterpret_cast<const uint32_t*>(p + 2 * CROW);
-      const uint32_t r3 = *reinterpret_cast<const uint32_t*>(p + 3 * CROW);
-      // t01 = [r0.b0 r1.b0 r0.b1 r1.b1], u01 = [r0.b2 r1.b2 r0.b3 r1.b3] (likewise r2/r3)
-      const uint32_t t01 = __builtin_amdgcn_perm(r1, r0, 0x05010400u);
-      const uint32_t t23 = __builtin_amdgcn_perm(r3, r2, 0x05010400u);
-      const uint32_t u01 = __builtin_amdgcn_perm(r1, r0, 0x07030602u);
-      const uint32_t u23 = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
-      uint32_t* o = reinterpret_cast<uint32_t*>(xt + (long long)(4 * fq) * XTS + 4 * rq);
-      o[0] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);             // feature 4fq+0, batch 4rq..4rq+3
-      o[XTS / 4] = __builtin_amdgcn_perm(t23, t01, 0x07060302u);       // 4fq+1
-      o[2 * XTS / 4] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);   // 4fq+2
-      o[3 * XTS / 4] = __builtin_amdgcn_perm(u23, u01, 0x07060302u);   // 4fq+3
     }
     __syncthreads();
   }
@@ -571,8 +559,7 @@ __device__ void copier(const Args& a, int cid, uint8_t* smem) {
 // memory) and releases run k to the others, or stops the launch after `idle`
 // ticks without one (or on door < 0) and reports that to the host; copiers
 // 0..13 each move 8 batch rows of the run's pinned record into device stage
-// slot (st & 1): row-major image, the x^T bytes of those rows (4x4 v_perm
-// transposes), labels + lr (copier 0); every store write-through (sc1), then
+// slot (st & 1): row-major image, labels + lr (copier 0); every store write-through (sc1), then
 // every wave's vmcnt(0), the barrier and one agent add to the staged count.
 __device__ void copier_res(const Args& a, int cid, uint8_t* smem) {
   if (cid >= NCOPR) return;
@@ -641,33 +628,13 @@ __device__ void copier_res(const Args& a, int cid, uint8_t* smem) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(smem + rr * CROW + 16 * cc);
       __builtin_amdgcn_raw_buffer_store_b128(v, region_rsrc(dst, (int)REC), (r0 + rr) * DIN + 16 * cc, 0, 16);
     }
-    // x^T: feature quad fq x row quad rq (2 per copier) -> 4 dwords of 4 batch bytes
-    for (int t = tid; t < (DIN / 4) * (RR / 4); t += THREADS) {
-      const int fq = t >> 1, rq = t & 1;
-      const uint8_t* p = smem + 4 * rq * CROW + 4 * fq;
-      const uint32_t q0 = *reinterpret_cast<const uint32_t*>(p);
-      const uint32_t q1 = *reinterpret_cast<const uint32_t*>(p + CROW);
-      const uint32_t q2 = *reinterpret_cast<const uint32_t*>(p + 2 * CROW);
-      const uint32_t q3 = *reinterpret_cast<const uint32_t*>(p + 3 * CROW);
-      const uint32_t t01 = __builtin_amdgcn_perm(q1, q0, 0x05010400u);
-      const uint32_t t23 = __builtin_amdgcn_perm(q3, q2, 0x05010400u);
-      const uint32_t u01 = __builtin_amdgcn_perm(q1, q0, 0x07030602u);
-      const uint32_t u23 = __builtin_amdgcn_perm(q3, q2, 0x07030602u);
-      const auto rs = region_rsrc(dst, (int)REC);
-      const int o = (int)XROW_BYTES + (4 * fq) * XTS + r0 + 4 * rq;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(t23, t01, 0x05040100u), rs, o, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(t23, t01, 0x07060302u), rs, o + XTS, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(u23, u01, 0x05040100u), rs, o + 2 * XTS, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(u23, u01, 0x07060302u), rs, o + 3 * XTS, 0, 16);
-    }
     if (cid == 0 && tid < 32) {   // labels (dwords 0..27) and the run's lr (byte RES_LR_BYTE), loaded with the rows
       uint32_t v = lv;
       if (4 * tid != RES_LR_BYTE) {
         const int nv = B - 4 * tid;   // valid label bytes in this dword
         if (nv < 4) v = nv <= 0 ? 0u : (v & ((1u << (8 * nv)) - 1u));
       }
-      __builtin_amdgcn_raw_buffer_store_b32(v, region_rsrc(dst, (int)REC), (int)(XROW_BYTES + XT_BYTES) + 4 * tid, 0,
-                                            16);
+      __builtin_amdgcn_raw_buffer_store_b32(v, region_rsrc(dst, (int)REC), (int)XROW_BYTES + 4 * tid, 0, 16);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -807,6 +774,9 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
   for (int k = tid; k < 3 * 16 * LS; k += THREADS) a2T[k] = 0.f;   // a2T, dz2T, dz3T (batch pad stays 0)
   if constexpr (SPLIT)
     for (int k = tid; k < 3 * 16 * PS; k += THREADS) dzp[k] = (uint16_t)0;   // dz2 planes (batch pad 0)
+  // image rows 112..127: never staged, read by the weight gradient's last chunk
+  for (int k = tid; k < (XTS - BROWS) * XF_ROW / 16; k += THREADS)
+    *reinterpret_cast<u32x4*>(smem + L_XF + BROWS * XF_ROW + 16 * k) = u32x4{0u, 0u, 0u, 0u};
   const bool failed_in = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
 
   // x operands of the wave's feature tiles (registers, read from the LDS stage):
@@ -842,27 +812,20 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
   };
   // local tile of k (an absent second tile reads local tile 0: staged, never used)
   auto tlk = [=](int k) { return k ? (tv1 ? w + 8 : 0) : w; };
-  // wave 7: step st's slice -> LDS.  x rows: lane-linear [row][13 tiles] (rows of
-  // 208 B, conflict-free reads); x^T rows of the slice's features are contiguous
-  // in the stage, their 16-B batch chunks XOR-swizzled by (feature >> 1) & 7 on the
-  // source address so the fragment reads below are conflict-free
-  auto stage_x = [&](int st, int n0, int dn) {   // pieces n0, n0 + dn, ... of each part
+  // wave 7: step st's slice -> LDS, lane-linear [row][13 tiles] (rows of 208 B:
+  // conflict-free for the forward's dword reads and the weight gradient's
+  // transposing reads alike).  One image serves both GEMMs.
+  auto stage_x = [&](int st, int n0, int dn) {   // pieces n0, n0 + dn, ...
     const uint8_t* rec = a.stage + (long long)st * REC;
     const uint8_t* xr = rec + 16 * tile0(q);
-#pragma unroll 1   // a rolled loop: unrolled, the 49 pieces' addresses get hoisted out of the step loop
+#pragma unroll 1   // a rolled loop: unrolled, the 23 pieces' addresses get hoisted out of the step loop
     for (int n = n0; n < (XF_CHUNKS + 63) / 64; n += dn) {
       const int k = 64 * n + lane;
-      // q = 3's 13th tile reads the next row's first 16 B (inside the record): unused
+      // q = 3's 13th tile reads the next row's first 16 B (row 111: the first 16
+      // label bytes; inside the record either way): unused
       if (k < XF_CHUNKS) glds16(xr + (k / 13) * DIN + 16 * (k % 13), smem + L_XF + 1024 * n);
     }
-    const uint8_t* xtb = rec + XROW_BYTES + (long long)(16 * tile0(q)) * XTS;
-#pragma unroll 1
-    for (int n = n0; n < XT_CHUNKS / 64; n += dn) {
-      const int f = 8 * n + (lane >> 3);
-      const int s = (lane & 7) ^ ((f >> 1) & 7);
-      if (f < 16 * nt) glds16(xtb + f * XTS + 16 * s, smem + L_XT + 1024 * n);
-    }
-    if (n0 == 0 && lane < 8) glds16(rec + XROW_BYTES + XT_BYTES + 16 * lane, smem + L_LAB);
+    if (n0 == 0 && lane < 8) glds16(rec + XROW_BYTES + 16 * lane, smem + L_LAB);
   };
   auto read_xf = [&](int& lb) {
 #pragma unroll
@@ -872,22 +835,33 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         xf[k][b] = *reinterpret_cast<const uint32_t*>(smem + L_XF + (16 * b + r) * XF_ROW + 16 * tlk(k) + 4 * g);
     lb = smem[L_LAB + 16 * (w < NBT ? w : NBT - 1) + r];
   };
+  // The x^T fragments come out of the row-major image through ds_read_b64_tr_b8:
+  // per 16-lane group the 16 lanes' 8-byte pieces, in lane order, form an 8 x 16
+  // byte block (lanes 2i, 2i + 1 = its row i, wherever they point), and lane i
+  // gets column i, rows 0..7 in byte order (observed on MI355X with
+  // scripts/probes/tr8_probe.hip, both modes).  Lane (r, g) supplies byte
+  // 16 tile + 8 (r & 1) of a row picked so that the block's rows are the lane's K
+  // order, and receives feature 16 tile + r of those 8 batch rows:
+  //   SPLIT: row 32c + 8g + (r >> 1) -> batch 32c + 8g .. + 7.  Rows of 208 B = 52
+  //     dwords: the 16 rows x 4 dwords of a 32-lane half fall on 64 distinct banks.
+  //   else:  row 32c + 16 (r >> 3) + 4g + ((r >> 1) & 3) -> the lo dword is batch
+  //     tile 2c's rows 4g .. + 3, the hi dword tile 2c + 1's (tile 7: zero rows,
+  //     dropped); rows 16 apart share banks, a 2-way conflict on 8 reads a step.
+  //     (The consecutive-row read + permlane exchange of the dwords between lane
+  //     groups gave the same operands and cost this engine 0.9 us a step.)
+  // Needs EXEC all ones: every call is wave-uniform.
   auto read_xt = [&]() {
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) v2i lds_v2i;
+    const int row = SPLIT ? 8 * g + (r >> 1) : 16 * (r >> 3) + 4 * g + ((r >> 1) & 3);
 #pragma unroll
     for (int k = 0; k < NTW; ++k) {
-      const int f = 16 * tlk(k) + r;
-      if constexpr (SPLIT) {
+      const uint8_t* blk = smem + L_XF + row * XF_ROW + 16 * tlk(k) + 8 * (r & 1);
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-          const uint2 v = *reinterpret_cast<const uint2*>(
-              smem + L_XT + f * XTS + 16 * ((2 * cc + (g >> 1)) ^ ((f >> 1) & 7)) + 8 * (g & 1));
-          xt[k][2 * cc] = v.x;
-          xt[k][2 * cc + 1] = v.y;
-        }
-      } else {
-#pragma unroll
-        for (int s = 0; s < NBT; ++s)
-          xt[k][s] = *reinterpret_cast<const uint32_t*>(smem + L_XT + f * XTS + 16 * (s ^ ((f >> 1) & 7)) + 4 * g);
+      for (int cc = 0; cc < 4; ++cc) {
+        const v2i v = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i*)(blk + 32 * cc * XF_ROW));
+        xt[k][2 * cc] = (uint32_t)v.x;
+        if (2 * cc + 1 < XTN) xt[k][2 * cc + 1] = (uint32_t)v.y;
       }
     }
   };
@@ -1022,7 +996,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
   // vmcnt(0) + barrier; one lane polls that count with sc1 loads, the workgroup
   // barrier follows, and every load of the record is an sc1 load to registers
   // (MI355X_MICROARCH.md "Valid forms", first table row) -> the LDS layout of
-  // stage_x (x^T chunks XOR-swizzled).  false: stop (idle / door < 0 / error).
+  // stage_x.  false: stop (idle / door < 0 / error).
   auto res_stage = [&](int st) -> bool {
     int* rflag = abort_flag + 2;
     if (tid == 0) {
@@ -1051,18 +1025,8 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (k / 13) * DIN + 16 * (k % 13) + xr0, 0, 16);
       *reinterpret_cast<u32x4*>(smem + L_XF + 16 * k) = v;
     }
-    const int xt0 = (int)XROW_BYTES + 16 * tile0(q) * XTS;
-#pragma unroll 4
-    for (int k = tid; k < XT_CHUNKS; k += THREADS) {
-      const int f = k >> 3;
-      if (f < 16 * nt) {
-        const int sw = (k & 7) ^ ((f >> 1) & 7);
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, xt0 + f * XTS + 16 * sw, 0, 16);
-        *reinterpret_cast<u32x4*>(smem + L_XT + 16 * k) = v;
-      }
-    }
     if (tid < 8) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(XROW_BYTES + XT_BYTES) + 16 * tid, 0, 16);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)XROW_BYTES + 16 * tid, 0, 16);
       *reinterpret_cast<u32x4*>(smem + L_LAB + 16 * tid) = v;
     }
     __syncthreads();
