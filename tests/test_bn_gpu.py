@@ -74,10 +74,12 @@ def test_resnet50_fused_bn_step_trains(native):
 
 
 def test_bn_bwd_parts_fused_launch_many_shapes(native):
-    """bn_bwd_parts (finalize + apply in one launch, blocks synchronised by a
-    rotating pool of 256 monotonic counters) called 600 times with channel
-    counts alternating 64 / 256 / 2048 -- every slot of the pool is reused with a
-    different number of finalize blocks -- against the fp32 formula."""
+    """bn_bwd_parts (two plain launches: bn_bwd_finalize, then bn_bwd_apply)
+    called 600 times with single-row partials (P = 1) and channel counts
+    alternating 64 / 256 / 2048, i.e. the finalize's FC = 4 / 4 / 16 forms in
+    turn; dx, dgamma and dbeta of every 97th call and of the last three are
+    compared with the fp32 formula.  Multi-row partials and per-element bounds:
+    tests/test_bn_edges_gpu.py."""
     C_ = native
     cl = torch.channels_last
     cases = []
