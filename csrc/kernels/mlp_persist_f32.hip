@@ -43,10 +43,16 @@
 //          the step's x^T operands of P2 in the E1 window (wave 7: behind its
 //          stage DMA), the NEXT step's x operands of P0 where the staged step is
 //          read (wave 7: behind its stage DMA; the head waves: after P2, once
-//          wave 7's flag says the stage landed; the launch's first step in the
-//          prologue; a launch's last step prepares nothing).  P0 is split8 +
-//          MFMAs, and only the dz2 piece reads sit between a head flag and a
-//          chunk's MFMAs.  Same operands, same order: same bits.
+//          wave 7's flag says the stage landed -- it lands inside their E2 gather
+//          by now, but preparing between two polls there did not pay, see PREP
+//          in compute(); the launch's first step in the prologue; a launch's
+//          last step prepares nothing).  P0 is split8 + MFMAs, and only the dz2
+//          piece reads sit between a head flag and a chunk's MFMAs.  Same
+//          operands, same order: same bits.
+//      Workgroup 0's metrics (same engine, MET_FAST in compute()): its wave 7
+//          reduces the per-row loss / accuracy in front of barrier A, which made
+//          workgroup 0 the last to publish at every E1; the same sums by VALU
+//          lane permutes, and the ring slot by a 32-bit modulo.
 //    One LDS barrier and two inter-workgroup edges per step; the data of
 //    every edge is double-buffered by step parity and tagged with the global
 //    exchange sequence number, so buffers are never reset between launches.
@@ -242,7 +248,8 @@ struct Args {
                             // numerics; what the per-step LDS-DMA stage costs the hand-offs), bit 1 = head
                             // sub-phase stamps (slots 13-15, wave 0), bit 2 = wave 7 too prepares the next
                             // step's operands on the late path, after P2 (same bits as its early path:
-                            // tests/test_mlp_persist_operand_prep_gpu.py)
+                            // tests/test_mlp_persist_operand_prep_gpu.py), bit 3 = step-boundary stamps
+                            // of every wave (PHB below; needs phase_ts)
 };
 
 // resident per-run stamp (s_memrealtime, 100 MHz) -- profiling only: 0 copier 0
@@ -266,6 +273,16 @@ struct Args {
   if ((dbg & 2) != 0) { PH(ph); }
 #define PH7(ph) \
   if ((dbg & 2) == 0) { PH(ph); }
+// DTF_PERSIST_DBG bit 3: step-boundary stamps of every wave, lane 0, in the 16
+// slots of the unused workgroup row 32 + c (the rows of c keep wave 0's stamps):
+// w = wave w arrives at barrier A, 8 + w = head wave w done (flag set), 15 = wave
+// 7's W2 / b1 / b2 updates stored.  Wave 7's slot 15 of row c is then its last
+// chunk's MFMAs issued (not the stage landing)
+#define PHB(slot)                                                                                \
+  if constexpr (INS) {                                                                           \
+    if ((dbg & 8) != 0 && a.phase_ts != nullptr && lane == 0 && st < 64)                         \
+      a.phase_ts[((long long)st * 64 + 32 + c) * 16 + (slot)] = (long long)__builtin_amdgcn_s_memrealtime(); \
+  }
 
 // The exact three-way split v = hi + mid + lo by truncation, as fp32 bit
 // patterns whose low 16 bits are zero: hi keeps v's top 8 significant bits, the
@@ -795,12 +812,23 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
   //  XA[k][c] : weight-gradient A operands of this step, made from xt in the E1 window
   //  lab_n    : the next step's label until this step's head has used `lab`
   // P0 then starts with split8 and its MFMAs, and chunk() has only the dz2 piece
-  // reads between a head flag and its MFMAs.  The head waves have no early path:
-  // the stage lands 0.8-2.8 us after their E2 publish (mid-head), never inside the
-  // E2 window, and converting in the idle polls between chunks measured slower
-  // than the late path (profiles/mlp_persist_f32_operand_prep_ab.json).
+  // reads between a head flag and its MFMAs.  The head waves have no early path.
+  // Since the transposing reads halved the stage it lands inside their E2 gather
+  // (~0.4 us after the E2 publish), and preparing there between two polls, once
+  // wave 7's flag is up, was built and measured: 18-36 % of the head waves took
+  // it, every one found its granules there when it came back, and it gained
+  // 0.5 % alone and nothing on top of MET_FAST below
+  // (profiles/mlp_persist_f32_step_boundary_ab.json).  Converting in the idle
+  // polls between chunks measured slower than the late path as well
+  // (profiles/mlp_persist_f32_operand_prep_ab.json).
   // (the N-GPU split kernels sit at 225-227 VGPRs: not applied there)
   constexpr bool PREP = SPLIT && !RES && NW == 1;
+  // MET_FAST (same engine): workgroup 0's loss / accuracy reduction sits in wave
+  // 7's tail in front of barrier A, where it made workgroup 0 arrive ~0.5 us after
+  // the other 27 at every step (profiles/mlp_persist_f32_step_boundary_ab.json) --
+  // the same sums through VALU lane permutes instead of 12 LDS round trips, and a
+  // 32-bit ring slot instead of a 64-bit modulo per step
+  constexpr bool MET_FAST = PREP;
   bf16x8 XF[NBT], XA[NTW][4];
   int lab_n = 0;
   // an operand stays where it was made (the compiler neither sinks the
@@ -1068,6 +1096,13 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
     if (c == 0 && tid >= 272 && tid < 272 + NCLS) put(a.p_b2 + (tid - 272), b2s[tid - 272]);
   };
 
+  // MET_FAST: the metric ring slot of the launch's first step (workgroup 0), so a
+  // step's slot is a 32-bit modulo (ring and the launch's steps are both < 2^31)
+  unsigned mslot0 = 0u;
+  if constexpr (MET_FAST) {
+    if (c == 0) mslot0 = (unsigned)(gstep0 % a.ring);
+  }
+
   const PeerRs<NW> prs = peer_rsrcs<NW>(a.peer_base, MULTI ? a.W : 1);
   bool aborted = false;
   for (int st = 0; st < a.nsteps; ++st) {
@@ -1128,6 +1163,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       for (int b = 0; b < NBT; ++b) zbuf[(w * NBT + b) * 64 + lane] = acc[b];
     }
     if (w == 0) { PH(1); }
+    PHB(w);
     lds_barrier();
     if (w == 0) { PH(2); }
     const bool more = !RES && st + 1 < a.nsteps;   // RES: the next run's record is staged at its top
@@ -1146,7 +1182,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
       if (lane == 0) __hip_atomic_store(hflag + 7, st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      PH7(15);
+      if ((dbg & 8) == 0) { PH7(15); }
     } else if (w == 7 && more && lane == 0) {
       __hip_atomic_store(hflag + 7, st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -1314,6 +1350,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         __hip_atomic_store(reinterpret_cast<int*>(smem + L_HFLAG) + w, st + 1, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_WORKGROUP);
       if (w == 0) { PH(9); }
+      PHB(8 + w);
     }
     // ---------------- P2 without a workgroup barrier: a wave multiplies the weight-
     // gradient chunk of batch rows 32cc..32cc+31 (one batch tile without SPLIT) as
@@ -1405,6 +1442,9 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
     f32x4 D = {0.f, 0.f, 0.f, 0.f};      // wave 7: dW2[16j+4g+i][class r] (x B)
     float gb = 0.f;                      // wave 7: db1 (lanes < 16) / db2 (lanes 16..25) (x B)
     if (w == 7) {
+      if constexpr (INS) {
+        if ((dbg & 8) != 0) { PH7(15); }
+      }
       // lanes 16..25: db2 column lane - 16 (lanes < 16 take db1 from the ones tile)
       const float* gsrc = rdb2 + (lane >= 16 && lane < 16 + NCLS ? lane - 16 : 0);
       const f32x4* dw2p = reinterpret_cast<const f32x4*>(smem + L_DW2P);
@@ -1419,10 +1459,24 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       if (c == 0) {   // loss / accuracy of the batch: per-row values, fixed reduction order
         const float* rl = reinterpret_cast<const float*>(smem + L_RLOSS);
         const bool hi = lane + 64 < BROWS;
-        const float ls = wave_sum(rl[lane] + (hi ? rl[lane + 64] : 0.f));
-        const float cr = wave_sum(rl[128 + lane] + (hi ? rl[128 + lane + 64] : 0.f));
+        // MET_FAST: wave_sum's butterfly (lane ^ 32, 16, 8, 4, 2, 1) without its LDS
+        // round trips.  After the ^32 and ^16 steps a row's rotation by 8 is its ^8
+        // partner, and from then on the values repeat with the period of the next
+        // partner distance, so the rotations by 4, 2, 1 fetch what ^4, ^2, ^1 would:
+        // the same additions, the same bits in every lane
+        auto wsum = [&](float v) {
+          if constexpr (MET_FAST) {
+            v += xor32(v);
+            v += xor16(v);
+            return row16_sum(v);
+          } else {
+            return wave_sum(v);
+          }
+        };
+        const float ls = wsum(rl[lane] + (hi ? rl[lane + 64] : 0.f));
+        const float cr = wsum(rl[128 + lane] + (hi ? rl[128 + lane + 64] : 0.f));
         if (lane == 63) {
-          const int sl = (int)((gstep0 + st) % a.ring);
+          const int sl = MET_FAST ? (int)((mslot0 + (unsigned)st) % (unsigned)a.ring) : (int)((gstep0 + st) % a.ring);
           if constexpr (RES) {   // workgroup 0 publishes them (LDS), the ring keeps them too
             reinterpret_cast<float*>(abort_flag)[4] = ls / (float)B;
             reinterpret_cast<float*>(abort_flag)[5] = cr / (float)B;
@@ -1444,6 +1498,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
           b2s[lane - 16] -= lrB * gb;
         }
       }
+      PHB(15);
     }
     if (*abort_flag) { aborted = true; break; }   // final for this step: every head has reported
     if (more && !prepped) {

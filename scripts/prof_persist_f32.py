@@ -9,9 +9,14 @@ piece reads and MFMAs follow), 11 weight-gradient MFMAs done (and, on the late
 path, the next step's operands read and converted), 12 update done.
 Wave 7, lane 0: 13 last head tile folded, 14 step start, 15 next step's stage
 landed in LDS (absent in a launch's last step).  The one-GPU split engine
-converts the step's weight-gradient operands inside E1_wait and, when the stage
-has landed by then, the next step's forward operands inside E2_wait
-(DTF_PERSIST_DBG=4 forces the late path after P2).
+converts the step's weight-gradient operands inside E1_wait.  The next step's
+forward operands: wave 7 behind its own stage DMA (early path), the head waves
+after P2, inside wgrad_mfma -- they have no early path (DTF_PERSIST_DBG=4 puts
+wave 7 on the late path too).
+DTF_PERSIST_DBG=8 adds the step-boundary stamps of every wave (step_boundary
+below: arrivals at barrier A, head-done times, wave 7's tail, workgroup 0's
+wave 7 against the others'); slot 15 is then wave 7's last chunk, not the stage
+landing.
 Prints the median / p90 of every segment over steps 1..63 and all compute
 workgroups, plus per-step time and launch-level timing.
 """
@@ -30,6 +35,42 @@ from distributed_tensorflow_example_amd.models import mlp  # noqa: E402
 
 NAMES = {"fp32": ["fwd_mfma", "barrier_A", "E1_publish", "E1_wait", "E1_load_sum", "P1_logit_publish",
                        "E2_wait", "E2_load_sum", "head", "head_to_first_chunk", "wgrad_mfma", "update"]}
+
+
+def step_boundary(raw, nwg):
+    """DTF_PERSIST_DBG=8: the step boundary of every wave, us from wave 0's start
+    of the same step (steps 1..G-2; the barrier a step's tail runs into is the
+    next step's).  raw: [step][64 rows][16] ticks -- see PHB in the kernel."""
+    us = raw.astype(np.float64) * 0.01
+    G = raw.shape[0]
+    s = np.arange(1, G - 1)
+    b0, b1 = us[:, :nwg], us[:, 32:32 + nwg]
+    t0 = b0[s, :, 0][:, :, None]                       # [step][wg][1]
+    med = lambda x: round(float(np.median(x)), 3)
+    p90 = lambda x: round(float(np.percentile(x, 90)), 3)
+    arr = b1[s + 1, :, 0:8] - t0                       # arrival at the NEXT step's barrier A
+    last = arr.argmax(axis=2)
+    hd = b1[s, :, 8:15] - t0
+    w7 = {"last_chunk_issued": b0[s, :, 15], "fold_done": b0[s, :, 13], "updates_stored": b1[s, :, 15],
+          "next_step_start": b0[s + 1, :, 14], "next_barrier_A_arrival": b1[s + 1, :, 7]}
+    o = {
+        "next_barrier_A_arrival_us_median_by_wave": [med(arr[:, :, w]) for w in range(8)],
+        "last_arriver_fraction_by_wave": [round(float((last == w).mean()), 4) for w in range(8)],
+        "last_arrival_minus_wave0_arrival_us_median_p90": [med(arr.max(2) - arr[:, :, 0]), p90(arr.max(2) - arr[:, :, 0])],
+        "wave7_arrival_minus_latest_head_wave_us_median_p90": [med(arr[:, :, 7] - arr[:, :, :7].max(2)),
+                                                                 p90(arr[:, :, 7] - arr[:, :, :7].max(2))],
+        "head_done_us_median_by_wave": [med(hd[:, :, w]) for w in range(7)],
+        "head_done_spread_in_workgroup_us_median_p90": [med(hd.max(2) - hd.min(2)), p90(hd.max(2) - hd.min(2))],
+        "last_head_done_us_median": med(hd.max(2)),
+        "wave7_us_median": {k: med(v - t0[:, :, 0]) for k, v in w7.items()},
+        "wave7_last_head_done_to_last_chunk_issued_us_median": med(w7["last_chunk_issued"] - t0[:, :, 0] - hd.max(2)),
+    }
+    upd = b1[s, :, 15]
+    nxt = b1[s + 1, :, 7]
+    o["workgroup0_wave7_behind_median_of_others_us_median"] = {
+        "updates_stored": med(upd[:, 0] - np.median(upd[:, 1:], axis=1)),
+        "next_barrier_A_arrival": med(nxt[:, 0] - np.median(nxt[:, 1:], axis=1))}
+    return o
 
 
 def main():
@@ -108,6 +149,8 @@ def main():
             out["head_detail_us_from_logits_summed"] = {
                 "softmax_done": med(rs[:, :, 13] - rs[:, :, 8]), "da_mfma_done": med(rs[:, :, 14] - rs[:, :, 8]),
                 "dz2_planes_rowsums_done": med(rs[:, :, 15] - rs[:, :, 8]), "head_done": med(rs[:, :, 9] - rs[:, :, 8])}
+        elif int(os.environ.get("DTF_PERSIST_DBG", "0")) & 8:
+            out["step_boundary"] = step_boundary(ts.cpu().numpy().reshape(65, 64, 16)[:G], nj * nq)
         else:
             staged = rs[:-1]            # the launch's last step stages nothing
             lead = staged[:, :, 6] - staged[:, :, 15]
