@@ -16,7 +16,8 @@ hipError_t dtfk_hogwild_gather_rows(const long long* ids, int n, int D, const fl
                                    hipStream_t s);
 hipError_t dtfk_sparse_rows_apply(float* table, float* slot_a, float* slot_b, const long long* rows, const float* g,
                                   long long n, int D, int kind, float lr, float mu, int nesterov, float rho, float eps,
-                                  const int* skip, hipStream_t s);
+                                  float lr_power, float l1, float l2, float l2_shrinkage, const int* skip,
+                                  hipStream_t s);
 hipError_t dtfk_hogwild_scatter_sgd(const long long* ids, const float* g, int n, int D, float* const* shards, int W,
                                     float lr, int locking, hipStream_t s);
 hipError_t dtfk_bucket_pack(const float* g, uint16_t* c, int64_t n, float scale, int fp16, hipStream_t s);
@@ -594,10 +595,12 @@ static void hogwild_scatter_sgd(at::Tensor ids, at::Tensor grads, int64_t shards
 }
 
 // Row-sparse optimizer update of a table shard (sparse_optim.hip): rows[i] >= 0
-// distinct (the owner summed the duplicates), -1 = no update.
+// distinct (the owner summed the duplicates), -1 = no update.  lr_power, l1,
+// l2, l2_shrinkage: kind 6 (FTRL) only.
 static void sparse_rows_apply(at::Tensor table, c10::optional<at::Tensor> slot_a, c10::optional<at::Tensor> slot_b,
                               at::Tensor rows, at::Tensor g, int kind, double lr, double mu, bool nesterov,
-                              double rho, double eps, c10::optional<at::Tensor> skip) {
+                              double rho, double eps, c10::optional<at::Tensor> skip, double lr_power, double l1,
+                              double l2, double l2_shrinkage) {
   f32c(table, "table"); i64c(rows, "rows"); f32c(g, "g");
   if (table.dim() != 2 || g.dim() != 2 || g.size(0) != rows.numel() || g.size(1) != table.size(1))
     throw std::runtime_error("sparse_rows_apply: table [R, D], g [n, D], rows [n]");
@@ -611,14 +614,16 @@ static void sparse_rows_apply(at::Tensor table, c10::optional<at::Tensor> slot_a
   ck(dtfk_sparse_rows_apply(table.data_ptr<float>(), opt_ptr<float>(slot_a), opt_ptr<float>(slot_b),
                             reinterpret_cast<const long long*>(rows.data_ptr<int64_t>()), g.data_ptr<float>(),
                             rows.numel(), (int)table.size(1), kind, (float)lr, (float)mu, nesterov ? 1 : 0,
-                            (float)rho, (float)eps, opt_ptr<int>(skip), cs()),
+                            (float)rho, (float)eps, (float)lr_power, (float)l1, (float)l2, (float)l2_shrinkage,
+                            opt_ptr<int>(skip), cs()),
      "sparse_rows_apply");
 }
 
 void init_ops(py::module& m) {
   m.def("sparse_rows_apply", &sparse_rows_apply, py::arg("table"), py::arg("slot_a"), py::arg("slot_b"),
         py::arg("rows"), py::arg("g"), py::arg("kind"), py::arg("lr"), py::arg("mu") = 0.0,
-        py::arg("nesterov") = false, py::arg("rho") = 0.9, py::arg("eps") = 1e-10, py::arg("skip") = py::none());
+        py::arg("nesterov") = false, py::arg("rho") = 0.9, py::arg("eps") = 1e-10, py::arg("skip") = py::none(),
+        py::arg("lr_power") = -0.5, py::arg("l1") = 0.0, py::arg("l2") = 0.0, py::arg("l2_shrinkage") = 0.0);
   m.def("hogwild_gather_rows", &hogwild_gather_rows, py::arg("ids"), py::arg("shards"), py::arg("W"), py::arg("out"));
   m.def("hogwild_scatter_sgd", &hogwild_scatter_sgd, py::arg("ids"), py::arg("grads"), py::arg("shards"), py::arg("W"),
         py::arg("lr"), py::arg("locking"));

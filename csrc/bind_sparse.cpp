@@ -11,7 +11,9 @@
 // which ran as a 36 us blit and cost ~40 us of host time per call on MI355X --
 // profiles/lr2_compat_r5.json).  Returns without waiting (staging slots are
 // double buffered behind events).  SparseLRPlan.step runs the same kernels on device
-// tensors (models/sparse_lr.py, one worker).
+// tensors (models/sparse_lr.py, one worker).  SparseLRPlan.set_ftrl switches
+// both entry points from scatter-SGD to the FTRL-Proximal update (slr_fwd + the
+// three slr_ftrl_* kernels); a plan without it runs what it always ran.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <pybind11/numpy.h>
@@ -36,6 +38,17 @@ hipError_t dtfk_slr_step_direct(float* W, long long F, const void* hids, int ids
                                 const float* hvals, const float* hlabels, void* ids_d, long long* off_d, float* vals_d,
                                 float* bias, int B, float lr_val, float* dz, float* lrow, float* loss_out, int* bad,
                                 void* gvar, int gkind, hipStream_t stream);
+hipError_t dtfk_slr_ftrl_step(float* W, long long F, const void* ids, int ids32, const long long* offsets,
+                              const float* vals, const float* labels, float* bias, int B, const float* lr_ptr,
+                              float lr_val, float* dz, float* lrow, float* loss_out, int* bad, void* gvar, int gkind,
+                              float* acc, float* lin, float* gsum, float* bslots, float lr_power, float l1, float l2,
+                              float shrink, hipStream_t stream);
+hipError_t dtfk_slr_ftrl_step_direct(float* W, long long F, const void* hids, int ids32, const long long* hoffsets,
+                                     const float* hvals, const float* hlabels, void* ids_d, long long* off_d,
+                                     float* vals_d, float* bias, int B, float lr_val, float* dz, float* lrow,
+                                     float* loss_out, int* bad, void* gvar, int gkind, float* acc, float* lin,
+                                     float* gsum, float* bslots, float lr_power, float l1, float l2, float shrink,
+                                     hipStream_t stream);
 }
 
 namespace dtf {
@@ -88,6 +101,35 @@ class SparseLRPlan {
       if (evs_[i]) (void)hipEventDestroy(evs_[i]);
     }
     if (side_) (void)hipStreamDestroy(side_);
+  }
+
+  // From now on the step applies FTRL-Proximal instead of scatter-SGD.  accum /
+  // linear: W's slots (same shape); bias_slots: {bias accum, bias linear}.  The
+  // plan adds the dense gradient accumulator (W's size, zero between steps):
+  // memory is W + 3 arrays of W's size.
+  void set_ftrl(at::Tensor accum, at::Tensor linear, at::Tensor bias_slots, double lr_power, double l1, double l2,
+                double l2_shrinkage) {
+    for (const at::Tensor* t : {&accum, &linear})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == F_ &&
+                      t->get_device() == W_.get_device(),
+                  "SparseLRPlan.set_ftrl: accum / linear must be contiguous fp32 GPU tensors of W's size");
+    TORCH_CHECK(bias_slots.is_cuda() && bias_slots.scalar_type() == at::kFloat && bias_slots.is_contiguous() &&
+                    bias_slots.numel() == 2,
+                "SparseLRPlan.set_ftrl: bias_slots must be two fp32 GPU values");
+    TORCH_CHECK(lr_power <= 0 && l1 >= 0 && l2 >= 0 && l2_shrinkage >= 0,
+                "SparseLRPlan.set_ftrl: learning_rate_power <= 0 and l1, l2, l2_shrinkage >= 0");
+    acc_ = accum;
+    lin_ = linear;
+    bslots_ = bias_slots;
+    gsum_ = at::zeros({F_}, W_.options());
+    hp_[0] = (float)lr_power, hp_[1] = (float)l1, hp_[2] = (float)l2, hp_[3] = (float)l2_shrinkage;
+    ftrl_ = true;
+  }
+  bool ftrl() const { return ftrl_; }
+  // the FTRL step's gradient accumulator (all 0.0 between steps)
+  at::Tensor grad_accumulator() const {
+    TORCH_CHECK(ftrl_, "SparseLRPlan.grad_accumulator: not an FTRL plan");
+    return gsum_;
   }
 
   // lr2.py's feeds (numpy).  False: not applicable (dtypes, shapes, a row index
@@ -270,14 +312,26 @@ class SparseLRPlan {
         if (feed_ == 0) {
           // the forward kernel reads the slot in place and leaves device copies for the apply
           const char* hd = static_cast<const char*>(hdev_[slot]);
-          hck(dtfk_slr_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
-                                   reinterpret_cast<const long long*>(hd + o_off),
-                                   reinterpret_cast<const float*>(hd + o_val), reinterpret_cast<const float*>(hd + o_lab),
-                                   d + o_ids, reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
-                                   bias_.data_ptr<float>(), (int)B, (float)lr, dz_.data_ptr<float>(),
-                                   lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
-                                   gs_.ptr, gs_.kind, st),
-              "SparseLRPlan: step");
+          if (ftrl_) {
+            hck(dtfk_slr_ftrl_step_direct(
+                    W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
+                    reinterpret_cast<const long long*>(hd + o_off), reinterpret_cast<const float*>(hd + o_val),
+                    reinterpret_cast<const float*>(hd + o_lab), d + o_ids, reinterpret_cast<long long*>(d + o_off),
+                    reinterpret_cast<float*>(d + o_val), bias_.data_ptr<float>(), (int)B, (float)lr,
+                    dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
+                    gs_.ptr, gs_.kind, acc_.data_ptr<float>(), lin_.data_ptr<float>(), gsum_.data_ptr<float>(),
+                    bslots_.data_ptr<float>(), hp_[0], hp_[1], hp_[2], hp_[3], st),
+                "SparseLRPlan: FTRL step");
+          } else {
+            hck(dtfk_slr_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
+                                     reinterpret_cast<const long long*>(hd + o_off),
+                                     reinterpret_cast<const float*>(hd + o_val), reinterpret_cast<const float*>(hd + o_lab),
+                                     d + o_ids, reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
+                                     bias_.data_ptr<float>(), (int)B, (float)lr, dz_.data_ptr<float>(),
+                                     lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
+                                     gs_.ptr, gs_.kind, st),
+                "SparseLRPlan: step");
+          }
           hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
           pending_[slot] = true;
         } else if (feed_ == 3) {
@@ -350,6 +404,15 @@ class SparseLRPlan {
  private:
   void launch(const void* ids, bool i32, const long long* offs, const float* vals, const float* labels, int B,
               float lr, hipStream_t st) {
+    if (ftrl_) {
+      hck(dtfk_slr_ftrl_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels,
+                             bias_.data_ptr<float>(), B, nullptr, lr, dz_.data_ptr<float>(), lrow_.data_ptr<float>(),
+                             loss_.data_ptr<float>(), bad_.data_ptr<int>(), gs_.ptr, gs_.kind, acc_.data_ptr<float>(),
+                             lin_.data_ptr<float>(), gsum_.data_ptr<float>(), bslots_.data_ptr<float>(), hp_[0], hp_[1],
+                             hp_[2], hp_[3], st),
+          "SparseLRPlan: FTRL step");
+      return;
+    }
     hck(dtfk_slr_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, bias_.data_ptr<float>(), B, nullptr,
                       lr, dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(),
                       bad_.data_ptr<int>(), gs_.ptr, gs_.kind, st),
@@ -357,6 +420,9 @@ class SparseLRPlan {
   }
 
   at::Tensor W_, bias_, gstep_, loss_, bad_, dev_, dz_, lrow_;
+  at::Tensor acc_, lin_, bslots_, gsum_;   // set_ftrl: W's slots, the bias's two, the gradient accumulator
+  bool ftrl_ = false;
+  float hp_[4] = {-0.5f, 0.f, 0.f, 0.f};   // learning_rate_power, l1, l2, l2_shrinkage
   void* hbuf_[2] = {nullptr, nullptr};
   void* hdev_[2] = {nullptr, nullptr};
   int64_t hcap_[2] = {0, 0};
@@ -382,6 +448,10 @@ void init_sparse(py::module& m) {
            py::arg("lr"))
       .def("step", &SparseLRPlan::step, py::arg("labels"), py::arg("offsets"), py::arg("ids"), py::arg("vals"),
            py::arg("lr"))
+      .def("set_ftrl", &SparseLRPlan::set_ftrl, py::arg("accum"), py::arg("linear"), py::arg("bias_slots"),
+           py::arg("lr_power") = -0.5, py::arg("l1") = 0.0, py::arg("l2") = 0.0, py::arg("l2_shrinkage") = 0.0)
+      .def("ftrl", &SparseLRPlan::ftrl)
+      .def("grad_accumulator", &SparseLRPlan::grad_accumulator)
       .def("loss", &SparseLRPlan::loss)
       .def("runs", &SparseLRPlan::runs)
       .def("timing", &SparseLRPlan::timing)

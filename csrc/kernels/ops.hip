@@ -10,10 +10,11 @@
 //   embedding_bag_bwd scatter-add / fused scatter-SGD      (K10 backward + K8 sparse apply)
 //   argmax_correct    accuracy counter                     (K7)
 //   auc_hist          streaming_auc confusion histograms   (K12)
-//   multi-tensor SGD / momentum / Adam (TF epsilon-hat semantics) / AdamW   (K8, K9)
+//   multi-tensor SGD / momentum / Adam (TF epsilon-hat semantics) / AdamW / Adagrad / RMSProp / FTRL   (K8, K9)
 // Every kernel is wave64-native: one wave per row/bag where rows are
 // independent, shuffles over 64 lanes, no warp-32 idioms.
 #include "common.h"
+#include "ftrl.h"
 
 namespace dtfk {
 namespace ops {
@@ -627,7 +628,9 @@ __device__ __forceinline__ float ld_grad(const void* g, int64_t i, int gbf) {
 }
 
 // kind 0: sgd, 1: momentum (use_nesterov in flags bit0), 2: adam (TF), 3: adamw,
-// 4: adagrad (TF; m = accumulator), 5: rmsprop (TF; m = mean square, v = momentum, b1 = decay)
+// 4: adagrad (TF; m = accumulator), 5: rmsprop (TF; m = mean square, v = momentum, b1 = decay),
+// 6: ftrl (TF ApplyFtrlV2, ftrl.h; m = accum, v = linear; the float arguments carry
+//    b1 = learning_rate_power, b2 = l1, eps = l2, wd = l2_shrinkage)
 __global__ void multi_tensor_apply(const TensorRec* __restrict__ tab, const int2* __restrict__ chunks,
                                    int nchunks, int kind, int gbf, const float* __restrict__ lr_ptr,
                                    float lr_scalar, float gscale, float wd, float b1, float b2, float eps,
@@ -670,6 +673,8 @@ __global__ void multi_tensor_apply(const TensorRec* __restrict__ tab, const int2
       m = ms;
       v = mo;
       p -= mo;
+    } else if (kind == 6) {
+      ftrl_update(p, m, v, g, lr, -b1, b2, eps, wd);
     } else {
       if (kind == 2 && wd != 0.f) g += wd * p;
       const float mv = b1 * m + (1.f - b1) * g;
@@ -680,7 +685,7 @@ __global__ void multi_tensor_apply(const TensorRec* __restrict__ tab, const int2
       if (kind == 3 && wd != 0.f) p -= lr * wd * p0;
     }
   };
-  const bool use_m = kind != 0, use_v = kind == 2 || kind == 3 || kind == 5;
+  const bool use_m = kind != 0, use_v = kind == 2 || kind == 3 || kind == 5 || kind == 6;
   // 16-byte path (4 elements per access) when every stream of this chunk is aligned:
   // the scalar loop moved 4 B per lane per access (~4.5 TB/s on BERT-base's AdamW)
   const bool vec = (s & 3) == 0 && (reinterpret_cast<uintptr_t>(t.p) & 15) == 0 &&

@@ -1,4 +1,4 @@
-// Reached by: sharded-table sparse optimizers (Wide&Deep sparse_opt=adagrad/rmsprop/momentum); tests/test_sparse_optim_gpu.py
+// Reached by: sharded-table sparse optimizers (Wide&Deep sparse_opt=adagrad/rmsprop/momentum/ftrl); tests/test_sparse_optim_gpu.py, test_ftrl_gpu.py
 // Row-sparse optimizer updates of a sharded embedding table, on its owner
 // (parallel/sharded_embedding.py: ShardedEmbedding.set_optimizer).
 //
@@ -13,6 +13,7 @@
 //   kind 1  Momentum         acc = mu acc + g;  var -= lr acc   (Nesterov: lr (g + mu acc))
 //   kind 4  Adagrad          acc += g^2;        var -= lr g / sqrt(acc)
 //   kind 5  RMSProp          ms = rho ms + (1-rho) g^2;  mom = mu mom + lr g / sqrt(ms + eps);  var -= mom
+//   kind 6  FTRL-Proximal    TF's SparseApplyFtrl(V2), a = accum, b = linear (ftrl.h)
 //
 // (kind numbers = optim.KINDS).  rows[i] < 0 marks an entry with no update
 // (exchange padding, the non-first copies of a duplicated row).  Rows with
@@ -21,6 +22,7 @@
 // per thread when D % 4 == 0.  `skip` (device int32, may be null): a voided
 // step (sharded-exchange overflow) changes nothing.
 #include "common.h"
+#include "ftrl.h"
 
 namespace dtfk {
 namespace sparse_optim {
@@ -28,6 +30,7 @@ namespace sparse_optim {
 struct Hyper {
   float lr, mu, rho, eps;
   int kind, nesterov;
+  float p, l1, l2, shrink;   // FTRL: p = -learning_rate_power >= 0, l1, l2, l2_shrinkage
 };
 
 __device__ __forceinline__ void update1(float& var, float& a, float& b, float g, const Hyper& h) {
@@ -45,7 +48,7 @@ __device__ __forceinline__ void update1(float& var, float& a, float& b, float g,
       var -= h.lr * g * rsqrtf(acc);
       break;
     }
-    default: {   // 5: RMSProp, a = ms, b = mom
+    case 5: {   // RMSProp, a = ms, b = mom
       const float ms = h.rho * a + (1.f - h.rho) * g * g;
       const float mom = h.mu * b + h.lr * g * rsqrtf(ms + h.eps);
       a = ms;
@@ -53,6 +56,9 @@ __device__ __forceinline__ void update1(float& var, float& a, float& b, float g,
       var -= mom;
       break;
     }
+    default:   // 6: FTRL, a = accum, b = linear
+      ftrl_update(var, a, b, g, h.lr, h.p, h.l1, h.l2, h.shrink);
+      break;
   }
 }
 
@@ -94,13 +100,15 @@ __global__ __launch_bounds__(256) void rows_apply(float* __restrict__ table, flo
 
 extern "C" hipError_t dtfk_sparse_rows_apply(float* table, float* slot_a, float* slot_b, const long long* rows,
                                              const float* g, long long n, int D, int kind, float lr, float mu,
-                                             int nesterov, float rho, float eps, const int* skip, hipStream_t s) {
+                                             int nesterov, float rho, float eps, float lr_power, float l1, float l2,
+                                             float l2_shrinkage, const int* skip, hipStream_t s) {
   using namespace dtfk::sparse_optim;
   if (n <= 0 || D <= 0) return hipSuccess;
-  if (kind != 0 && kind != 1 && kind != 4 && kind != 5) return hipErrorInvalidValue;
-  if ((kind == 1 || kind == 4 || kind == 5) && slot_a == nullptr) return hipErrorInvalidValue;
-  if (kind == 5 && slot_b == nullptr) return hipErrorInvalidValue;
-  const Hyper h{lr, mu, rho, eps, kind, nesterov};
+  if (kind != 0 && kind != 1 && kind != 4 && kind != 5 && kind != 6) return hipErrorInvalidValue;
+  if ((kind == 1 || kind == 4 || kind == 5 || kind == 6) && slot_a == nullptr) return hipErrorInvalidValue;
+  if ((kind == 5 || kind == 6) && slot_b == nullptr) return hipErrorInvalidValue;
+  if (kind == 6 && (lr_power > 0.f || l1 < 0.f || l2 < 0.f || l2_shrinkage < 0.f)) return hipErrorInvalidValue;
+  const Hyper h{lr, mu, rho, eps, kind, nesterov, -lr_power, l1, l2, l2_shrinkage};
   const bool v4 = D % 4 == 0;
   const long long work = n * (v4 ? D / 4 : D);
   const unsigned grid = (unsigned)((work + 255) / 256);

@@ -161,17 +161,19 @@ class PartitionedSlot:
     is_partitioned = True
     op_type, attrs = "VariableV2", {}
 
-    def __init__(self, pv: PartitionedVariable, slot: str):
+    def __init__(self, pv: PartitionedVariable, slot: str, alias: Optional[str] = None):
+        """`alias`: the variable-name suffix when the optimizer was given one
+        (FtrlOptimizer's accum_name / linear_name); the table's slot key stays `slot`."""
         self.pv, self.slot = pv, slot
-        self.name = f"{pv.name[:-2]}/{slot}:0"
+        self.name = f"{pv.name[:-2]}/{alias or slot}:0"
         self.shape, self.rows, self.dim, self.dtype = pv.shape, pv.rows, pv.dim, torch.float32
         self.partitioner, self.world = pv.partitioner, pv.world
         self.trainable = False
         self.initialized = True
         self.placement = pv.placement
-        # the value the optimizer gives the slot (Adagrad: initial_accumulator_value, RMSProp ms: 1)
-        self.init = {"Adagrad": float(pv.table.opt_hp.get("initial_accumulator_value", 0.1)),
-                     "RMSProp": 1.0}.get(slot, 0.0)
+        # the value the optimizer gives the slot (Adagrad / FTRL accum: initial_accumulator_value, RMSProp ms: 1)
+        acc0 = float(pv.table.opt_hp.get("initial_accumulator_value", 0.1))
+        self.init = {"Adagrad": acc0, "Ftrl": acc0, "RMSProp": 1.0}.get(slot, 0.0)
 
     @property
     def table(self):

@@ -44,7 +44,7 @@ from .summary import FileWriter, SummaryWriter
 
 __all__ = [
     "ClusterSpec", "Server", "replica_device_setter", "GradientDescentOptimizer", "MomentumOptimizer",
-    "AdamOptimizer", "AdagradOptimizer", "RMSPropOptimizer", "SyncReplicasOptimizer", "Supervisor",
+    "AdamOptimizer", "AdagradOptimizer", "RMSPropOptimizer", "FtrlOptimizer", "SyncReplicasOptimizer", "Supervisor",
     "MonitoredTrainingSession", "MonitoredSession", "SingularMonitoredSession", "Scaffold", "Saver",
     "export_meta_graph", "read_meta_graph",
     "Coordinator", "QueueRunner", "start_queue_runners", "add_queue_runner", "batch", "shuffle_batch",
@@ -397,7 +397,7 @@ class Optimizer:
         pairs = list(grads_and_vars)
         dense_pairs = [(g, v) for g, v in pairs if not _is_pv(v)]
         sparse_pairs = [(g, v) for g, v in pairs if _is_pv(v)]
-        if sparse_pairs and self._kind not in ("sgd", "momentum", "adagrad", "rmsprop", "adam"):
+        if sparse_pairs and self._kind not in ("sgd", "momentum", "adagrad", "rmsprop", "adam", "ftrl"):
             raise NotImplementedError(f"{type(self).__name__}: no sparse (partitioned-variable) update rule")
         for _, pv in sparse_pairs:      # owner-side sparse rule + sharded slots (TF names var/<slot>)
             pv.table.set_optimizer(self._kind, **self._sparse_hp())
@@ -542,7 +542,7 @@ class Optimizer:
         g = get_default_graph()
         names = {v.name for v in g.get_collection(GLOBAL_VARIABLES)}
         for sname in pv.table.slots:
-            sv = PartitionedSlot(pv, sname)
+            sv = PartitionedSlot(pv, sname, self._slot_alias(sname))
             if sv.name not in names:
                 g.add_to_collection(GLOBAL_VARIABLES, sv)
 
@@ -559,6 +559,11 @@ class Optimizer:
 
     def get_slot_names(self):
         return list(self._slot_names)
+
+    def _slot_alias(self, sname: str) -> Optional[str]:
+        """The variable-name suffix of a sharded table's slot `sname` when it is
+        not the slot's own name (FtrlOptimizer's accum_name / linear_name)."""
+        return None
 
     def _register_nonslot(self, dense_vars, pvs):
         """TF's non-slot optimizer variables (Adam: beta1_power / beta2_power)."""
@@ -730,6 +735,52 @@ class RMSPropOptimizer(Optimizer):
 
     def _slot_init(self, sname: str) -> float:
         return 1.0 if sname == "RMSProp" else 0.0      # TF initialises the mean square to ones
+
+
+class FtrlOptimizer(Optimizer):
+    """tf.train.FtrlOptimizer: FTRL-Proximal with L1 / L2 and the V2 shrinkage
+    term (ApplyFtrlV2 / SparseApplyFtrlV2).  Slots `<var>/Ftrl` (accum, starts at
+    initial_accumulator_value) and `<var>/Ftrl_1` (linear, starts at 0)."""
+
+    _kind = "ftrl"
+
+    def __init__(self, learning_rate, learning_rate_power=-0.5, initial_accumulator_value=0.1,
+                 l1_regularization_strength=0.0, l2_regularization_strength=0.0, use_locking=False, name="Ftrl",
+                 accum_name=None, linear_name=None, l2_shrinkage_regularization_strength=0.0):
+        super().__init__(learning_rate, use_locking, name)
+        if initial_accumulator_value < 0.0:
+            raise ValueError(f"initial_accumulator_value {initial_accumulator_value} needs to be positive or zero")
+        if learning_rate_power > 0.0:
+            raise ValueError(f"learning_rate_power {learning_rate_power} needs to be negative or zero")
+        if l1_regularization_strength < 0.0:
+            raise ValueError(f"l1_regularization_strength {l1_regularization_strength} needs to be positive or zero")
+        if l2_regularization_strength < 0.0:
+            raise ValueError(f"l2_regularization_strength {l2_regularization_strength} needs to be positive or zero")
+        if l2_shrinkage_regularization_strength < 0.0:
+            raise ValueError(f"l2_shrinkage_regularization_strength {l2_shrinkage_regularization_strength} needs to "
+                             "be positive or zero")
+        self.lr_power, self.init_acc = float(learning_rate_power), float(initial_accumulator_value)
+        self.l1, self.l2 = float(l1_regularization_strength), float(l2_regularization_strength)
+        self.l2_shrinkage = float(l2_shrinkage_regularization_strength)
+        # TF: slot names default to the optimizer's name (<var>/Ftrl, <var>/Ftrl_1)
+        accum = accum_name or self.name
+        linear = linear_name or self.name
+        self._slot_names = (accum, linear + "_1" if linear == accum else linear)
+
+    def _make_fused(self, params):
+        return _optim.FusedFtrl(params, self._lr_value(), self.lr_power, self.init_acc, self.l1, self.l2,
+                                self.l2_shrinkage)
+
+    def _sparse_hp(self):
+        return {"learning_rate_power": self.lr_power, "initial_accumulator_value": self.init_acc,
+                "l1_regularization_strength": self.l1, "l2_regularization_strength": self.l2,
+                "l2_shrinkage_regularization_strength": self.l2_shrinkage}
+
+    def _slot_init(self, sname: str) -> float:
+        return self.init_acc if sname == self._slot_names[0] else 0.0
+
+    def _slot_alias(self, sname: str) -> Optional[str]:
+        return self._slot_names[0 if sname == "Ftrl" else 1]
 
 
 class SyncReplicasOptimizer(Optimizer):

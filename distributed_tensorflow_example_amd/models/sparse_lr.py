@@ -15,6 +15,19 @@ scatter-SGD apply.  Synchronous semantics: the loss is the mean over the
 union of all workers' batches, so each owner applies lr/W times the sum of
 the per-worker mean gradients (== lr x the global-batch gradient when the
 per-worker batches are equal).
+
+`optimizer="ftrl"` trains W and b with tf.train.FtrlOptimizer's rule instead
+(FTRL-Proximal with L1: the optimizer lr2's data paths are named after; most
+weights of the table end at exactly 0).  Each owner sums the workers' mean
+gradients with the 1/W average as `grad_scale` (the rule is not linear in the
+gradient, so the average cannot be folded into the learning rate) and applies
+the row-sparse rule; b is a dense FTRL variable with two scalar slots.  On one
+GPU the step stays fused: slr_fwd and three kernels (gradient sum, one-writer
+rule, clear; csrc/kernels/sparse_lr.hip) that need the slots `Ftrl` and
+`Ftrl_1` and a dense gradient accumulator next to W -- memory is W + 3 arrays
+of W's size, 16 GB at F = 1e9.  One difference from TF there: an entry whose
+value is exactly 0 is padding to the fused step and touches nothing, where TF
+would still recompute the weight of a real zero-valued feature from `linear`.
 """
 from __future__ import annotations
 
@@ -33,10 +46,19 @@ class SparseLRTrainer(StaticStepMixin):
                  init_std: float = 1.0, device=None, auc_bins: int = 200, ids_capacity: Optional[int] = None,
                  rows: int = 500, peer_capacity: Optional[int] = None, update_mode: Optional[str] = None,
                  use_locking: bool = False, table: Optional[ShardedEmbedding] = None,
-                 bias: Optional[torch.Tensor] = None):
+                 bias: Optional[torch.Tensor] = None, optimizer: str = "sgd", optimizer_hp: Optional[dict] = None):
         """`table` / `bias`: train existing storage in place instead of creating
         it (the compat Session's lowered lr2 graph: a PartitionedVariable's
-        shards and the `bias/Variable` tensor, compat/lowering.py)."""
+        shards and the `bias/Variable` tensor, compat/lowering.py).
+        `optimizer`: "sgd" (the reference's GradientDescentOptimizer) or "ftrl"
+        (tf.train.FtrlOptimizer; `optimizer_hp`: learning_rate_power,
+        initial_accumulator_value, l1_regularization_strength,
+        l2_regularization_strength, l2_shrinkage_regularization_strength)."""
+        if optimizer not in ("sgd", "ftrl"):
+            raise ValueError(f"SparseLRTrainer: optimizer must be 'sgd' or 'ftrl', not '{optimizer}'")
+        if optimizer == "sgd" and optimizer_hp:
+            raise ValueError("SparseLRTrainer: optimizer_hp needs optimizer='ftrl'")
+        self.optimizer, self.optimizer_hp = optimizer, dict(optimizer_hp or {})
         self.world = world or get_world()
         self.device = torch.device(device) if device is not None else self.world.device
         self.lr = float(lr)
@@ -68,6 +90,21 @@ class SparseLRTrainer(StaticStepMixin):
         from ..parallel import async_ps
         self.update_mode = async_ps.update_mode(update_mode)
         self._bstore = None
+        self.b_slots = self._bopt = None
+        if optimizer == "ftrl":
+            if self.update_mode == "async" and self.world.world_size > 1:
+                raise NotImplementedError("asynchronous (Hogwild) updates: SGD only")
+            from .. import optim
+            from ..parallel.sharded_embedding import ftrl_kwargs
+            self.W.set_optimizer("ftrl", **self.optimizer_hp)     # checks the hyper-parameters as TF does
+            # the bias is an FTRL variable of its own: {accum, linear} in one tensor (the fused step's layout)
+            acc0 = float(self.optimizer_hp.get("initial_accumulator_value", 0.1))
+            self.b_slots = torch.tensor([acc0, 0.0], dtype=torch.float32, device=self.device)
+            kw = ftrl_kwargs(self.optimizer_hp)
+            self._bopt = optim.FusedFtrl([self.b.data], self.lr, kw["lr_power"], acc0, kw["l1"], kw["l2"],
+                                         kw["l2_shrinkage"])
+            self._bopt.m[0], self._bopt.v[0] = self.b_slots[0:1], self.b_slots[1:2]
+            self._gb = torch.zeros_like(self.b.data)
         if self.update_mode == "async" and self.world.world_size > 1:
             self.W.hogwild = async_ps.HogwildTable(self.W, self.world, use_locking=use_locking)
             self._bstore = async_ps.HogwildStore([self.b.data], self.world, use_locking=use_locking)
@@ -129,6 +166,10 @@ class SparseLRTrainer(StaticStepMixin):
         if plan is None:
             from .. import _native
             plan = self._plan = _native.load().SparseLRPlan(self.W.local, self.b.data, None)
+            if self.optimizer == "ftrl":
+                from ..parallel.sharded_embedding import ftrl_kwargs
+                plan.set_ftrl(self.W.slots["Ftrl"], self.W.slots["Ftrl_1"], self.b_slots,
+                              **ftrl_kwargs(self.optimizer_hp))
         host = _host_arrays(labels, offsets, ids, vals)
         if host is not None and plan.run_csr(*host, self.lr):
             self.global_step += 1
@@ -179,7 +220,7 @@ class SparseLRTrainer(StaticStepMixin):
             return self._train_step((labels, offsets, ids, vals))
 
         def state():
-            st = [self.W.local, self.b.data]
+            st = self.W.state_tensors() + [self.b.data] + ([self.b_slots] if self.b_slots is not None else [])
             return st + (self.W.router.state() if self.W.router is not None else [])
         self._graphed = GraphedStep(step, state, strict=strict)
         self._example = self._static_batch(example if example is not None else self._zero_batch())
@@ -202,6 +243,15 @@ class SparseLRTrainer(StaticStepMixin):
         loss.backward()
         ws = self.world.world_size
         g = rows.grad if rows.grad is not None else torch.zeros_like(rows)
+        if self.optimizer == "ftrl":
+            # the rule is not linear in the gradient: the 1/W average is a grad_scale, not folded into lr
+            self.W.apply_sgd(ctx, g, self.lr, grad_scale=1.0 / ws)
+            with torch.no_grad():
+                self._gb.copy_(self.b.grad)
+                if ws > 1:
+                    self.world.all_reduce(self._gb)
+                self._bopt.step([self._gb], grad_scale=1.0 / ws, skip=ctx.void)   # a voided step changes nothing
+            return loss.detach()
         self.W.apply_sgd(ctx, g, self.lr / ws)
         with torch.no_grad():
             gb = self.b.grad.clone()
@@ -245,6 +295,11 @@ class SparseLRTrainer(StaticStepMixin):
         self.sync_exchange()
         local = {"weights/Variable": self.W}      # saved as a TF partitioned variable
         repl = {"bias/Variable": self.b.detach(), "global_step": torch.tensor(float(self.global_step))}
+        if self.optimizer == "ftrl":              # TF's slot names: <var>/Ftrl (accum), <var>/Ftrl_1 (linear)
+            for slot in ("Ftrl", "Ftrl_1"):
+                local[f"weights/Variable/{slot}"] = self.W.slot_view(slot)
+            repl["bias/Variable/Ftrl"] = self.b_slots[0:1].detach()
+            repl["bias/Variable/Ftrl_1"] = self.b_slots[1:2].detach()
         return local, repl
 
 

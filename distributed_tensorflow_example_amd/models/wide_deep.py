@@ -15,7 +15,7 @@ sized for 288 GB HBM per shard); the dense tower is replicated and its
 gradients travel in one flat bucket all-reduce (RCCL over xGMI) that is
 launched on a side stream while the sparse all-to-all updates run.
 Embedding rows use sparse SGD (the ps-side ScatterSub of TF) or TF's sparse
-Adagrad / Momentum / RMSProp / Adam rules (`sparse_opt`, applied by the row
+Adagrad / Momentum / RMSProp / FTRL / Adam rules (`sparse_opt`, applied by the row
 owner: ShardedEmbedding.set_optimizer), the tower uses SGD or TF-Adam
 through the fused multi-tensor kernel.
 """
@@ -54,7 +54,7 @@ class WideDeep(StaticStepMixin):
         self.emb = ShardedEmbedding(num_features, emb_dim, self.world, init_std=emb_std, seed=seed + 1,
                                     device=self.device, name="deep/embedding", capacity=ids_capacity,
                                     router=self.wide.router)
-        # the tables' owner-side rule: sgd (TF ScatterSub) | adagrad | momentum | rmsprop | adam
+        # the tables' owner-side rule: sgd (TF ScatterSub) | adagrad | momentum | rmsprop | ftrl | adam
         for t in (self.wide, self.emb):
             t.set_optimizer(sparse_opt, **(sparse_hp or {}))
         self.rows = int(rows)              # batch rows of the captured step

@@ -15,6 +15,9 @@ Semantics follow TensorFlow where the reference uses it:
   Adagrad (TF)     acc += g^2; p -= lr*g/sqrt(acc)      (acc starts at 0.1)
   RMSProp (TF)     ms = rho*ms + (1-rho)*g^2; mom = mu*mom + lr*g/sqrt(ms+eps); p -= mom
                    (ms starts at 1, as TF's RMSPropOptimizer initialises it)
+  FTRL (TF, V2)    acc' = acc + g^2; linear += g + 2*shrink*p - (acc'^q - acc^q)/lr * p;
+                   p = |linear| > l1 ? (sign(linear)*l1 - linear) / (acc'^q/lr + 2*l2) : 0
+                   (q = -learning_rate_power; acc starts at 0.1, linear at 0; exact zeros under l1)
 `grad_scale` folds the 1/N of a summed all-reduce into the update.
 CPU tensors use the same math in PyTorch (CPU/gloo configuration).
 """
@@ -28,7 +31,7 @@ from .. import _native
 
 _bump_version = torch.autograd.graph.increment_version
 
-KINDS = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 3, "adagrad": 4, "rmsprop": 5}
+KINDS = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 3, "adagrad": 4, "rmsprop": 5, "ftrl": 6}
 
 
 _F32_TINY = 1.1754943508222875e-38   # smallest normal float32
@@ -77,6 +80,23 @@ def _same_layout(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a.shape == b.shape and all(x == y for x, y, n in zip(a.stride(), b.stride(), a.shape) if n > 1)
 
 
+def ftrl_torch_(var, acc, lin, g, lr, lr_power=-0.5, l1=0.0, l2=0.0, l2_shrinkage=0.0):
+    """TF's ApplyFtrl(V2) in place on float32 tensors (csrc/kernels/ftrl.h, same
+    operation order); g: the duplicate-summed, unshrunk gradient."""
+    p = -float(lr_power)
+    pw = (lambda a: a.sqrt()) if p == 0.5 else ((lambda a: torch.ones_like(a)) if p == 0.0 else (lambda a: a.pow(p)))
+    gs = g + 2.0 * l2_shrinkage * var if l2_shrinkage != 0.0 else g
+    an = acc + g * g
+    pn = pw(an)
+    sigma = (pn - pw(acc)) / lr
+    l = lin + gs - sigma * var
+    quad = pn / lr + 2.0 * l2
+    step = (torch.sign(l) * l1 - l) / quad
+    var.copy_(torch.where(l.abs() > l1, step, torch.zeros_like(step)))   # a select: the untaken 0 / 0 never lands
+    acc.copy_(an)
+    lin.copy_(l)
+
+
 class _FusedBase:
     kind = "sgd"
 
@@ -91,9 +111,9 @@ class _FusedBase:
         self.momentum, self.nesterov = momentum, nesterov
         self.lr_t = torch.tensor([float(lr)], dtype=torch.float32, device=self.device)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        need_m = self.kind in ("momentum", "adam", "adamw", "adagrad", "rmsprop")
-        need_v = self.kind in ("adam", "adamw", "rmsprop")
-        m0 = {"adagrad": self._init_acc(), "rmsprop": 1.0}.get(self.kind, 0.0)
+        need_m = self.kind in ("momentum", "adam", "adamw", "adagrad", "rmsprop", "ftrl")
+        need_v = self.kind in ("adam", "adamw", "rmsprop", "ftrl")
+        m0 = {"adagrad": self._init_acc(), "rmsprop": 1.0, "ftrl": self._init_acc()}.get(self.kind, 0.0)
         self.m = [torch.full_like(p, m0, dtype=torch.float32) if need_m else None for p in self.params]
         self.v = [torch.zeros_like(p, dtype=torch.float32) if need_v else None for p in self.params]
         self._tab_key = None
@@ -236,6 +256,9 @@ class _FusedBase:
                 m.mul_(self.b1).add_((1 - self.b1) * g * g)
                 v.mul_(self.momentum).add_(lr * g / (m + self.eps).sqrt())
                 p.sub_(v)
+            elif self.kind == "ftrl":
+                # as the kernel reads them: b1 = learning_rate_power, b2 = l1, eps = l2, wd = l2_shrinkage
+                ftrl_torch_(p, self.m[i], self.v[i], g, lr, self.b1, self.b2, self.eps, self.wd)
             else:
                 if self.kind == "adam" and self.wd:
                     g = g + self.wd * p
@@ -299,6 +322,30 @@ class FusedRMSProp(_FusedBase):
 
     def __init__(self, params, lr, decay=0.9, momentum=0.0, epsilon=1e-10):
         super().__init__(params, lr, beta1=decay, eps=epsilon, momentum=momentum)
+
+
+class FusedFtrl(_FusedBase):
+    """TF FtrlOptimizer (ApplyFtrlV2): m = accum (starts at initial_accumulator_value),
+    v = linear (starts at 0).  The multi-tensor kernel takes its hyper-parameters in
+    the float arguments the other kinds use: b1 = learning_rate_power, b2 = l1,
+    eps = l2, weight_decay = l2_shrinkage."""
+
+    kind = "ftrl"
+
+    def __init__(self, params, lr, learning_rate_power=-0.5, initial_accumulator_value=0.1, l1=0.0, l2=0.0,
+                 l2_shrinkage=0.0):
+        if initial_accumulator_value < 0.0:
+            raise ValueError("initial_accumulator_value needs to be positive or zero")
+        if learning_rate_power > 0.0:
+            raise ValueError("learning_rate_power needs to be negative or zero")
+        if l1 < 0.0 or l2 < 0.0 or l2_shrinkage < 0.0:
+            raise ValueError("l1, l2 and l2_shrinkage need to be positive or zero")
+        self._acc0 = float(initial_accumulator_value)
+        super().__init__(params, lr, weight_decay=float(l2_shrinkage), beta1=float(learning_rate_power),
+                         beta2=float(l1), eps=float(l2))
+
+    def _init_acc(self) -> float:
+        return self._acc0
 
 
 def global_grad_norm(grads: List[torch.Tensor]) -> torch.Tensor:

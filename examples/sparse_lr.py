@@ -15,7 +15,10 @@ Same flags and console lines as the reference (lr2.py:19-35, :307-315,
 * `--mode=queue` uses the native looping LibsvmStream (C++ threads), with
   `--steps_per_epoch` bounding an epoch (the reference loops forever);
 * `--checkpoint` writes a sharded TF V2 bundle at the end (lr2.py only
-  declares the flag).
+  declares the flag);
+* `--optimizer=ftrl` trains with tf.train.FtrlOptimizer's rule (`--l1`, `--l2`,
+  `--learning_rate_power`): the result JSON then reports `zero_share`, the
+  share of exactly-zero weights among the rows the training touched.
 """
 from __future__ import annotations
 
@@ -59,6 +62,10 @@ flags.DEFINE_string("update_mode", "", "sync (default: all-reduce / sharded exch
                     "reference's Hogwild ps updates: rows read from and scattered into the owners' shared shards); "
                     "'' = $DTF_UPDATE_MODE or sync")
 flags.DEFINE_boolean("use_locking", False, "async: no lost updates (CAS / file locks), TF's use_locking")
+flags.DEFINE_string("optimizer", "sgd", "sgd (lr2.py's GradientDescentOptimizer) or ftrl (tf.train.FtrlOptimizer)")
+flags.DEFINE_float("l1", 0.0, "ftrl: l1_regularization_strength")
+flags.DEFINE_float("l2", 0.0, "ftrl: l2_regularization_strength")
+flags.DEFINE_float("learning_rate_power", -0.5, "ftrl: learning_rate_power (<= 0)")
 FLAGS = flags.FLAGS
 
 
@@ -86,7 +93,12 @@ def main(_argv):
     dp.LoadData()
     log.info("build model")
     model = sparse_lr.SparseLRTrainer(FLAGS.features, FLAGS.learning_rate, world, seed=FLAGS.seed,
-                                      update_mode=FLAGS.update_mode or None, use_locking=FLAGS.use_locking)
+                                      update_mode=FLAGS.update_mode or None, use_locking=FLAGS.use_locking,
+                                      optimizer=FLAGS.optimizer,
+                                      optimizer_hp={"learning_rate_power": FLAGS.learning_rate_power,
+                                                    "l1_regularization_strength": FLAGS.l1,
+                                                    "l2_regularization_strength": FLAGS.l2}
+                                      if FLAGS.optimizer == "ftrl" else None)
     log.info("sampling test data ...")
     test_data = dp.GetTestSamplesSampled(sampling_rate=0.1, sampling_max_num=1000)
 
@@ -128,10 +140,18 @@ def main(_argv):
         local, repl = model.checkpoint_tensors()
         path = ckpt.save_sharded(FLAGS.checkpoint, local, repl, world, global_step=model.global_step)
         log.info(f"saved checkpoint {path}")
+    result = {"auc": auc, "loss": last_loss, "global_step": model.global_step,
+              "b": float(model.b.detach().cpu()[0]), "steps": step, "train_s": train_s}
+    if FLAGS.optimizer == "ftrl":
+        # rows seen = rows whose accumulator left its initial value (every worker's shard)
+        seen = model.W.slots["Ftrl"] != float(model.W.opt_hp.get("initial_accumulator_value", 0.1))
+        n_seen = world.host_all_reduce(float(seen.sum()))
+        n_zero = world.host_all_reduce(float((seen & (model.W.local == 0.0)).sum()))
+        result.update(optimizer="ftrl", rows_seen=int(n_seen), zero_share=n_zero / max(n_seen, 1.0))
+        log.info(f"ftrl: {int(n_zero)} of {int(n_seen)} seen weights are exactly zero")
     if FLAGS.result_json:
         with open(FLAGS.result_json, "w") as f:
-            json.dump({"auc": auc, "loss": last_loss, "global_step": model.global_step,
-                       "b": float(model.b.detach().cpu()[0]), "steps": step, "train_s": train_s}, f)
+            json.dump(result, f)
     dp.close()
     server.signal_done()
     return 0

@@ -84,8 +84,8 @@ def main():
     ap.add_argument("--nnz", type=int, default=32, help="features per sample")
     ap.add_argument("--gpus", type=int, default=None)
     ap.add_argument("--lr", type=float, default=None, help="sparse models: SGD learning rate")
-    ap.add_argument("--sparse-opt", default="sgd", choices=["sgd", "adagrad", "momentum", "rmsprop", "adam"],
-                    help="wide_deep: the tables' owner-side update rule")
+    ap.add_argument("--sparse-opt", default="sgd", choices=["sgd", "adagrad", "momentum", "rmsprop", "adam", "ftrl"],
+                    help="wide_deep: the tables' owner-side update rule; sparse_lr / lr2: sgd or ftrl")
     ap.add_argument("--graph", action="store_true", help="sparse_lr / lr2 / wide_deep: replay each step as one captured hipGraph")
     ap.add_argument("--trace-marker", action="store_true",
                     help="launch a spin kernel right before the timed loop, so a kernel trace can be cut to the "
@@ -122,13 +122,17 @@ def main():
     else:
         from distributed_tensorflow_example_amd.models.sparse_lr import SparseLRTrainer
 
-        m = SparseLRTrainer(a.features, 0.1 if a.lr is None else a.lr, w, ids_capacity=a.batch * a.nnz, rows=a.batch)
+        if a.sparse_opt not in ("sgd", "ftrl"):
+            ap.error("sparse_lr / lr2: --sparse-opt sgd or ftrl")
+        m = SparseLRTrainer(a.features, 0.1 if a.lr is None else a.lr, w, ids_capacity=a.batch * a.nnz, rows=a.batch,
+                            optimizer=a.sparse_opt)
         if a.graph:
             m.enable_graph()
         cfg = {"model": f"{'lr2 ' if a.model == 'lr2' else ''}sparse_lr F={a.features}",
                "global_batch": a.batch * w.world_size, "per_gpu_batch": a.batch, "lr": 0.1 if a.lr is None else a.lr,
                "seq_len": None, "parallelism": f"emb-shard{w.world_size}", "nnz_per_sample": a.nnz,
-               "graph": bool(a.graph)}
+               "graph": bool(a.graph), "sparse_opt": a.sparse_opt,
+               "fused_step": bool(m._fused_ok())}
     if dev.type == "cuda":
         torch.cuda.synchronize()
     init_s = time.time() - t_init
