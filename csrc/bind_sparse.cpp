@@ -14,6 +14,10 @@
 // tensors (models/sparse_lr.py, one worker).  SparseLRPlan.set_ftrl switches
 // both entry points from scatter-SGD to the FTRL-Proximal update (slr_fwd + the
 // three slr_ftrl_* kernels); a plan without it runs what it always ran.
+// SparseLRPlan.evaluate / eval_csr / eval_coo are the forward-only evaluation
+// (slr_eval_rows + slr_eval_reduce) of device tensors / the same host feeds:
+// packing, int32 ids and the two staging slots are the training step's
+// (submit_), the kernels read W and b only and add the batch to a device record.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <pybind11/numpy.h>
@@ -49,6 +53,10 @@ hipError_t dtfk_slr_ftrl_step_direct(float* W, long long F, const void* hids, in
                                      float* loss_out, int* bad, void* gvar, int gkind, float* acc, float* lin,
                                      float* gsum, float* bslots, float lr_power, float l1, float l2, float shrink,
                                      hipStream_t stream);
+hipError_t dtfk_slr_eval(const float* W, long long F, const void* ids, int ids32, const long long* offsets,
+                         const float* vals, const float* labels, float* labels_d, int direct, const float* bias, int B,
+                         float* lrow, float* prow, int* brow, int* bad, float* z_out, float* p_out, int T, int reset,
+                         long long* rec, hipStream_t stream);
 }
 
 namespace dtf {
@@ -135,6 +143,54 @@ class SparseLRPlan {
   // lr2.py's feeds (numpy).  False: not applicable (dtypes, shapes, a row index
   // outside [0, B)) -- nothing ran, the caller takes the general path.
   bool run(py::array y, py::array idx, py::array ids, py::array vals, double lr) {
+    return coo_(y, idx, ids, vals, true, [&](const Feed& f, hipStream_t st) { train_go_(f, lr, st); });
+  }
+
+  // A host CSR batch (the native trainer's own layout: labels [B] / [B, 1] f32,
+  // offsets [B + 1] i64, ids [nnz] i64, vals [nnz] f32 or None) through the same
+  // packed feed.  False: not applicable (dtypes / shapes / offsets not a CSR of nnz).
+  bool run_csr(py::array y, py::array offsets, py::array ids, py::object vals_o, double lr) {
+    return csr_(y, offsets, ids, vals_o, true, [&](const Feed& f, hipStream_t st) { train_go_(f, lr, st); });
+  }
+
+  // Forward-only evaluation of host feeds (run's / run_csr's arrays, packing
+  // and staging slots): the batch's loss sum, row count, out-of-range ids and
+  // streaming_auc histograms are added to `record` ({loss_sum (fp64 bits), rows,
+  // bad ids, pos[T + 1], neg[T + 1]}, int64 on the device; reset: start it over).
+  // pred / logits: optional [B] fp32 outputs (sigmoid(z), z).  Nothing of the
+  // training state changes.  False: a feed run / run_csr would refuse, nothing ran.
+  // The record and the outputs are checked first: a wrong record / pred / logits
+  // raises whatever the feed is.
+  bool eval_coo(py::array y, py::array idx, py::array ids, py::array vals, at::Tensor record, bool reset,
+                c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
+    const EvalOut o = eval_out_(y.size(), record, reset, pred, logits);
+    return coo_(y, idx, ids, vals, false, [&](const Feed& f, hipStream_t st) { eval_go_(f, o, st); });
+  }
+  bool eval_csr(py::array y, py::array offsets, py::array ids, py::object vals_o, at::Tensor record, bool reset,
+                c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
+    const EvalOut o = eval_out_(y.size(), record, reset, pred, logits);
+    return csr_(y, offsets, ids, vals_o, false, [&](const Feed& f, hipStream_t st) { eval_go_(f, o, st); });
+  }
+
+ private:
+  // one packed feed in its staging slot: h the pinned host slot, hd its device
+  // view, d the device copy; byte offsets of ids | offsets | values | labels
+  struct Feed {
+    char* h;
+    const char* hd;
+    char* d;
+    int64_t o_ids, o_off, o_val, o_lab, total;
+    int B, slot;
+    bool i32;
+  };
+  struct EvalOut {
+    long long* rec;
+    float *pred, *logits;
+    int T, reset;
+  };
+
+  template <typename Go>
+  bool coo_(py::array y, py::array idx, py::array ids, py::array vals, bool train, Go&& go) {
     if (!y.dtype().is(py::dtype::of<float>()) || !idx.dtype().is(py::dtype::of<int64_t>()) ||
         !ids.dtype().is(py::dtype::of<int64_t>()) || !vals.dtype().is(py::dtype::of<float>()))
       return false;
@@ -152,7 +208,7 @@ class SparseLRPlan {
     if (y.ndim() > 2 || ids.ndim() > 1 || vals.ndim() > 1 || (y.ndim() == 2 && y.shape(1) != 1 && y.shape(0) != 1))
       return false;
     const int64_t ys_el = (y.ndim() == 2 && y.shape(0) == 1) ? y.strides(1) : ys;
-    return submit_(B, n, lr, [&](int64_t* hoff, int64_t* hid, int32_t* hid32, float* hval, float* hlab, bool i32) {
+    return submit_(B, n, train, [&](int64_t* hoff, int64_t* hid, int32_t* hid32, float* hval, float* hlab, bool i32) {
       // rows -> CSR offsets: in row order (lr2.py's own feeds, as_tf_feed) the
       // offsets are the row boundaries, found in one pass; otherwise a stable
       // counting sort by row (the same bags: the 'sum' combiner)
@@ -205,13 +261,11 @@ class SparseLRPlan {
       }
       for (int64_t b = 0; b < B; ++b) hlab[b] = *reinterpret_cast<const float*>(yb + b * ys_el);
       return true;
-    });
+    }, go);
   }
 
-  // A host CSR batch (the native trainer's own layout: labels [B] / [B, 1] f32,
-  // offsets [B + 1] i64, ids [nnz] i64, vals [nnz] f32 or None) through the same
-  // packed feed.  False: not applicable (dtypes / shapes / offsets not a CSR of nnz).
-  bool run_csr(py::array y, py::array offsets, py::array ids, py::object vals_o, double lr) {
+  template <typename Go>
+  bool csr_(py::array y, py::array offsets, py::array ids, py::object vals_o, bool train, Go&& go) {
     if (!y.dtype().is(py::dtype::of<float>()) || !offsets.dtype().is(py::dtype::of<int64_t>()) ||
         !ids.dtype().is(py::dtype::of<int64_t>()))
       return false;
@@ -230,7 +284,7 @@ class SparseLRPlan {
     const int64_t ys = (y.ndim() == 2 && y.shape(0) == 1) ? y.strides(1) : (y.ndim() >= 1 ? y.strides(0) : 4);
     const int64_t os = offsets.strides(0), fs = ids.strides(0), vs = has_v ? vals.strides(0) : 4;
     if (y.ndim() > 2 || (y.ndim() == 2 && y.shape(1) != 1 && y.shape(0) != 1)) return false;
-    return submit_(B, n, lr, [&](int64_t* hoff, int64_t* hid, int32_t* hid32, float* hval, float* hlab, bool i32) {
+    return submit_(B, n, train, [&](int64_t* hoff, int64_t* hid, int32_t* hid32, float* hval, float* hlab, bool i32) {
       int64_t prev = 0;
       for (int64_t b = 0; b <= B; ++b) {
         const int64_t o = *reinterpret_cast<const int64_t*>(ob + b * os);
@@ -244,10 +298,9 @@ class SparseLRPlan {
       else for (int64_t j = 0; j < n; ++j) hval[j] = *reinterpret_cast<const float*>(vb + j * vs);
       for (int64_t b = 0; b < B; ++b) hlab[b] = *reinterpret_cast<const float*>(yb + b * ys);
       return true;
-    });
+    }, go);
   }
 
- private:
   // out-of-range ids are kept as such (the kernels count and skip them): in
   // int32 form anything outside [0, F) becomes -1
   void pack_ids_(int64_t* hid, int32_t* hid32, bool i32, const char* fb, int64_t fs, int64_t n) const {
@@ -267,25 +320,30 @@ class SparseLRPlan {
   }
 
   // Packs one batch (fill writes the CSR offsets, ids, values and labels into
-  // the pinned slot) with the GIL released, moves it to the device and launches
-  // the step.  False when fill refused the batch (nothing was launched).
-  template <typename Fill>
-  bool submit_(int64_t B, int64_t n, double lr, Fill&& fill) {
+  // the pinned slot) with the GIL released, then go(feed, stream) moves it to the
+  // device and launches the kernels -- the training step or the evaluation:
+  // both share the slots, their events and the device copy.  False when fill
+  // refused the batch (nothing was launched).  Only a training run counts in
+  // runs() / timing().
+  template <typename Fill, typename Go>
+  bool submit_(int64_t B, int64_t n, bool train, Fill&& fill, Go&& go) {
     // ids travel as int32 when the table has < 2^31 rows (lr2's F = 1e9 does): half the bytes
     const bool i32 = F_ < (1LL << 31);
     const int64_t isz = i32 ? 4 : 8;
-    const int64_t o_ids = 0, o_off = align16(isz * n), o_val = o_off + align16(8 * (B + 1)),
-                  o_lab = o_val + align16(4 * n), total = o_lab + align16(4 * B);
-    const int slot = slot_ ^ 1;
+    Feed f;
+    f.i32 = i32;
+    f.B = (int)B;
+    f.o_ids = 0, f.o_off = align16(isz * n), f.o_val = f.o_off + align16(8 * (B + 1));
+    f.o_lab = f.o_val + align16(4 * n), f.total = f.o_lab + align16(4 * B);
+    const int64_t total = f.total;
+    const int slot = f.slot = slot_ ^ 1;
     bool ok = true;
-    if (dz_.numel() < B) {
-      dz_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
-      lrow_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
-    }
+    if (train) ensure_rows_(B);
+    else ensure_eval_(B);
     at::Tensor& dvb = feed_ == 3 ? dev2_[slot] : dev_;   // overlap: one device copy per slot
     if (dvb.numel() < total) dvb = at::empty({std::max<int64_t>(total, 1 << 20)}, W_.options().dtype(at::kByte));
     hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    char* d = static_cast<char*>(dvb.data_ptr());
+    f.d = static_cast<char*>(dvb.data_ptr());
     {
       py::gil_scoped_release nogil;
       using clk = std::chrono::steady_clock;
@@ -302,62 +360,134 @@ class SparseLRPlan {
         hcap_[slot] = cap;
       }
       const auto tw = clk::now();   // slot wait (+ first-use allocation) | packing
-      char* h = static_cast<char*>(hbuf_[slot]);
-      ok = fill(reinterpret_cast<int64_t*>(h + o_off), reinterpret_cast<int64_t*>(h + o_ids),
-                reinterpret_cast<int32_t*>(h + o_ids), reinterpret_cast<float*>(h + o_val),
-                reinterpret_cast<float*>(h + o_lab), i32);
+      char* h = f.h = static_cast<char*>(hbuf_[slot]);
+      f.hd = static_cast<const char*>(hdev_[slot]);
+      ok = fill(reinterpret_cast<int64_t*>(h + f.o_off), reinterpret_cast<int64_t*>(h + f.o_ids),
+                reinterpret_cast<int32_t*>(h + f.o_ids), reinterpret_cast<float*>(h + f.o_val),
+                reinterpret_cast<float*>(h + f.o_lab), i32);
       if (ok) {
         slot_ = slot;
         const auto t1 = clk::now();
-        if (feed_ == 0) {
-          // the forward kernel reads the slot in place and leaves device copies for the apply
-          const char* hd = static_cast<const char*>(hdev_[slot]);
-          if (ftrl_) {
-            hck(dtfk_slr_ftrl_step_direct(
-                    W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
-                    reinterpret_cast<const long long*>(hd + o_off), reinterpret_cast<const float*>(hd + o_val),
-                    reinterpret_cast<const float*>(hd + o_lab), d + o_ids, reinterpret_cast<long long*>(d + o_off),
-                    reinterpret_cast<float*>(d + o_val), bias_.data_ptr<float>(), (int)B, (float)lr,
-                    dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
-                    gs_.ptr, gs_.kind, acc_.data_ptr<float>(), lin_.data_ptr<float>(), gsum_.data_ptr<float>(),
-                    bslots_.data_ptr<float>(), hp_[0], hp_[1], hp_[2], hp_[3], st),
-                "SparseLRPlan: FTRL step");
-          } else {
-            hck(dtfk_slr_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
-                                     reinterpret_cast<const long long*>(hd + o_off),
-                                     reinterpret_cast<const float*>(hd + o_val), reinterpret_cast<const float*>(hd + o_lab),
-                                     d + o_ids, reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
-                                     bias_.data_ptr<float>(), (int)B, (float)lr, dz_.data_ptr<float>(),
-                                     lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
-                                     gs_.ptr, gs_.kind, st),
-                "SparseLRPlan: step");
-          }
-          hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
-          pending_[slot] = true;
-        } else if (feed_ == 3) {
-          hck(dtfk_slr_stage(hdev_[slot], d, total, side_), "SparseLRPlan: feed staging");
-          hck(hipEventRecord(evs_[slot], side_), "SparseLRPlan: event");
-          hck(hipStreamWaitEvent(st, evs_[slot], 0), "SparseLRPlan: wait staging");
-          launch(d + o_ids, i32, reinterpret_cast<const long long*>(d + o_off), reinterpret_cast<const float*>(d + o_val),
-                 reinterpret_cast<const float*>(d + o_lab), (int)B, (float)lr, st);
-          hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");   // host + device slot free after the step
-          pending_[slot] = true;
-        } else {
-          if (feed_ == 2) hck(hipMemcpyAsync(d, h, (size_t)total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
-          else hck(dtfk_slr_stage(hdev_[slot], d, total, st), "SparseLRPlan: feed staging");
-          hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
-          pending_[slot] = true;
-          launch(d + o_ids, i32, reinterpret_cast<const long long*>(d + o_off), reinterpret_cast<const float*>(d + o_val),
-                 reinterpret_cast<const float*>(d + o_lab), (int)B, (float)lr, st);
+        go(f, st);
+        if (train) {
+          t_[2] += std::chrono::duration<double, std::micro>(tw - t0).count();
+          t_[0] += std::chrono::duration<double, std::micro>(t1 - tw).count();
+          t_[1] += std::chrono::duration<double, std::micro>(clk::now() - t1).count();
         }
-        t_[2] += std::chrono::duration<double, std::micro>(tw - t0).count();
-        t_[0] += std::chrono::duration<double, std::micro>(t1 - tw).count();
-        t_[1] += std::chrono::duration<double, std::micro>(clk::now() - t1).count();
       }
     }
     if (!ok) return false;
-    ++runs_;
+    if (train) ++runs_;
+    else ++eval_runs_;
     return true;
+  }
+
+  // the training step on a packed feed (the feed modes of DTF_SLR_FEED)
+  void train_go_(const Feed& f, double lr, hipStream_t st) {
+    const int slot = f.slot;
+    const int64_t o_ids = f.o_ids, o_off = f.o_off, o_val = f.o_val, o_lab = f.o_lab, total = f.total;
+    const bool i32 = f.i32;
+    const int B = f.B;
+    char* d = f.d;
+    if (feed_ == 0) {
+      // the forward kernel reads the slot in place and leaves device copies for the apply
+      const char* hd = f.hd;
+      if (ftrl_) {
+        hck(dtfk_slr_ftrl_step_direct(
+                W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
+                reinterpret_cast<const long long*>(hd + o_off), reinterpret_cast<const float*>(hd + o_val),
+                reinterpret_cast<const float*>(hd + o_lab), d + o_ids, reinterpret_cast<long long*>(d + o_off),
+                reinterpret_cast<float*>(d + o_val), bias_.data_ptr<float>(), B, (float)lr,
+                dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
+                gs_.ptr, gs_.kind, acc_.data_ptr<float>(), lin_.data_ptr<float>(), gsum_.data_ptr<float>(),
+                bslots_.data_ptr<float>(), hp_[0], hp_[1], hp_[2], hp_[3], st),
+            "SparseLRPlan: FTRL step");
+      } else {
+        hck(dtfk_slr_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
+                                 reinterpret_cast<const long long*>(hd + o_off),
+                                 reinterpret_cast<const float*>(hd + o_val), reinterpret_cast<const float*>(hd + o_lab),
+                                 d + o_ids, reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
+                                 bias_.data_ptr<float>(), B, (float)lr, dz_.data_ptr<float>(),
+                                 lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
+                                 gs_.ptr, gs_.kind, st),
+            "SparseLRPlan: step");
+      }
+      hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
+      pending_[slot] = true;
+    } else if (feed_ == 3) {
+      hck(dtfk_slr_stage(f.hd, d, total, side_), "SparseLRPlan: feed staging");
+      hck(hipEventRecord(evs_[slot], side_), "SparseLRPlan: event");
+      hck(hipStreamWaitEvent(st, evs_[slot], 0), "SparseLRPlan: wait staging");
+      launch(d + o_ids, i32, reinterpret_cast<const long long*>(d + o_off), reinterpret_cast<const float*>(d + o_val),
+             reinterpret_cast<const float*>(d + o_lab), B, (float)lr, st);
+      hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");   // host + device slot free after the step
+      pending_[slot] = true;
+    } else {
+      if (feed_ == 2) hck(hipMemcpyAsync(d, f.h, (size_t)total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
+      else hck(dtfk_slr_stage(f.hd, d, total, st), "SparseLRPlan: feed staging");
+      hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
+      pending_[slot] = true;
+      launch(d + o_ids, i32, reinterpret_cast<const long long*>(d + o_off), reinterpret_cast<const float*>(d + o_val),
+             reinterpret_cast<const float*>(d + o_lab), B, (float)lr, st);
+    }
+  }
+
+  // the evaluation on a packed feed: read in place from the pinned slot (the
+  // default feed mode; no staging copy), else staged on the caller's stream first
+  void eval_go_(const Feed& f, const EvalOut& o, hipStream_t st) {
+    const bool direct = feed_ == 0;
+    if (feed_ == 2) hck(hipMemcpyAsync(f.d, f.h, (size_t)f.total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
+    else if (!direct) hck(dtfk_slr_stage(f.hd, f.d, f.total, st), "SparseLRPlan: feed staging");
+    const char* src = direct ? f.hd : f.d;
+    eval_launch_(src + f.o_ids, f.i32, reinterpret_cast<const long long*>(src + f.o_off),
+                 reinterpret_cast<const float*>(src + f.o_val), reinterpret_cast<const float*>(src + f.o_lab), direct,
+                 f.B, o, st);
+    hck(hipEventRecord(ev_[f.slot], st), "SparseLRPlan: event");   // slot (and device copy) free after the kernels
+    pending_[f.slot] = true;
+  }
+
+  void eval_launch_(const void* ids, bool i32, const long long* offs, const float* vals, const float* labels,
+                    bool direct, int B, const EvalOut& o, hipStream_t st) {
+    float* e = esc_.data_ptr<float>();
+    const int64_t cap = esc_.numel() / 4;   // lrow | prow | labels | bad ids per row (int)
+    hck(dtfk_slr_eval(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, e + 2 * cap,
+                      direct ? 1 : 0, bias_.data_ptr<float>(), B, e, e + cap, reinterpret_cast<int*>(e + 3 * cap),
+                      bad_.data_ptr<int>(), o.logits, o.pred, o.T, o.reset, o.rec, st),
+        "SparseLRPlan: evaluation");
+  }
+
+  void ensure_rows_(int64_t B) {
+    if (dz_.numel() < B) {
+      dz_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
+      lrow_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
+    }
+  }
+  // A larger batch gets a larger scratch; the outgrown one is kept, not freed: a
+  // captured hipGraph of an evaluation holds its pointers (both kernels of a
+  // capture use the same scratch, so a replay stays right).  16 bytes per row.
+  void ensure_eval_(int64_t B) {
+    if (esc_.numel() >= 4 * B) return;
+    if (esc_.defined()) esc_old_.push_back(esc_);
+    esc_ = at::empty({4 * std::max<int64_t>(B, 1024)}, W_.options());
+  }
+
+  // the record (3 + 2 (T + 1) int64, T >= 2) and the optional [B] outputs of an evaluation
+  EvalOut eval_out_(int64_t B, const at::Tensor& record, bool reset, const c10::optional<at::Tensor>& pred,
+                    const c10::optional<at::Tensor>& logits) const {
+    TORCH_CHECK(record.is_cuda() && record.scalar_type() == at::kLong && record.is_contiguous() &&
+                    record.get_device() == W_.get_device() && record.numel() >= 9 && (record.numel() - 3) % 2 == 0,
+                "SparseLRPlan: record must be a contiguous int64 GPU tensor of 3 + 2 (T + 1) entries, T >= 2");
+    EvalOut o{reinterpret_cast<long long*>(record.data_ptr<int64_t>()), nullptr, nullptr,
+              (int)((record.numel() - 3) / 2 - 1), reset ? 1 : 0};
+    for (int k = 0; k < 2; ++k) {
+      const c10::optional<at::Tensor>& t = k == 0 ? pred : logits;
+      if (!t.has_value()) continue;
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == B &&
+                      t->get_device() == W_.get_device(),
+                  "SparseLRPlan: pred / logits must be contiguous fp32 GPU tensors of B entries");
+      (k == 0 ? o.pred : o.logits) = t->data_ptr<float>();
+    }
+    return o;
   }
 
  public:
@@ -374,15 +504,38 @@ class SparseLRPlan {
                       vals->numel() == ids.numel(), "vals");
       vp = vals->data_ptr<float>();
     }
-    if (dz_.numel() < B) {
-      dz_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
-      lrow_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
-    }
+    ensure_rows_(B);
     launch(ids.data_ptr(), false, reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()), vp,
            labels.data_ptr<float>(), (int)B, (float)lr, c10::hip::getCurrentHIPStream().stream());
     ++runs_;
     return loss();
   }
+
+  // Forward-only evaluation of a device batch (step's tensors and checks) into
+  // `record` (see eval_csr); W, b, the optimizer's slots, global_step, runs()
+  // and loss() are not touched.  Capturable in a hipGraph (no host read-back, no
+  // memset node): the capture holds the tensors' and the scratch's addresses.
+  void evaluate(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals,
+                at::Tensor record, bool reset, c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
+    TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kFloat && labels.is_contiguous(), "labels");
+    TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kLong && offsets.is_contiguous(), "offsets");
+    TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous(), "ids");
+    const int64_t B = labels.numel();
+    TORCH_CHECK(B >= 1 && B <= (1 << 30), "SparseLRPlan.evaluate: 1 <= B <= 2^30 rows");
+    TORCH_CHECK(offsets.numel() == B + 1, "SparseLRPlan.evaluate: offsets must hold B + 1 entries");
+    const float* vp = nullptr;
+    if (vals.has_value()) {
+      TORCH_CHECK(vals->is_cuda() && vals->scalar_type() == at::kFloat && vals->is_contiguous() &&
+                      vals->numel() == ids.numel(), "vals");
+      vp = vals->data_ptr<float>();
+    }
+    const EvalOut o = eval_out_(B, record, reset, pred, logits);
+    ensure_eval_(B);
+    eval_launch_(ids.data_ptr(), false, reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()), vp,
+                 labels.data_ptr<float>(), false, (int)B, o, c10::hip::getCurrentHIPStream().stream());
+    ++eval_runs_;
+  }
+  int64_t eval_runs() const { return eval_runs_; }
 
   at::Tensor loss() const { return loss_.select(0, 0); }   // the last run's mean loss (0-d, device)
   // host time per run() call, us: waiting for the staging slot (the GPU two
@@ -419,7 +572,7 @@ class SparseLRPlan {
         "SparseLRPlan: step");
   }
 
-  at::Tensor W_, bias_, gstep_, loss_, bad_, dev_, dz_, lrow_;
+  at::Tensor W_, bias_, gstep_, loss_, bad_, dev_, dz_, lrow_, esc_;   // esc_: the evaluation's per-row scratch
   at::Tensor acc_, lin_, bslots_, gsum_;   // set_ftrl: W's slots, the bias's two, the gradient accumulator
   bool ftrl_ = false;
   float hp_[4] = {-0.5f, 0.f, 0.f, 0.f};   // learning_rate_power, l1, l2, l2_shrinkage
@@ -431,11 +584,12 @@ class SparseLRPlan {
   hipEvent_t evs_[2] = {nullptr, nullptr};
   at::Tensor dev2_[2];
   std::vector<int64_t> cnt_;
+  std::vector<at::Tensor> esc_old_;   // outgrown evaluation scratch (see ensure_eval_)
   hipEvent_t ev_[2] = {nullptr, nullptr};
   bool pending_[2] = {false, false};
   GstepRef gs_;
   int slot_ = 0;
-  int64_t F_ = 0, runs_ = 0;
+  int64_t F_ = 0, runs_ = 0, eval_runs_ = 0;
   double t_[3] = {0, 0, 0};
 };
 
@@ -448,6 +602,13 @@ void init_sparse(py::module& m) {
            py::arg("lr"))
       .def("step", &SparseLRPlan::step, py::arg("labels"), py::arg("offsets"), py::arg("ids"), py::arg("vals"),
            py::arg("lr"))
+      .def("evaluate", &SparseLRPlan::evaluate, py::arg("labels"), py::arg("offsets"), py::arg("ids"), py::arg("vals"),
+           py::arg("record"), py::arg("reset"), py::arg("pred") = py::none(), py::arg("logits") = py::none())
+      .def("eval_csr", &SparseLRPlan::eval_csr, py::arg("y"), py::arg("offsets"), py::arg("ids"), py::arg("vals"),
+           py::arg("record"), py::arg("reset"), py::arg("pred") = py::none(), py::arg("logits") = py::none())
+      .def("eval_coo", &SparseLRPlan::eval_coo, py::arg("y"), py::arg("indices"), py::arg("ids"), py::arg("vals"),
+           py::arg("record"), py::arg("reset"), py::arg("pred") = py::none(), py::arg("logits") = py::none())
+      .def("eval_runs", &SparseLRPlan::eval_runs)
       .def("set_ftrl", &SparseLRPlan::set_ftrl, py::arg("accum"), py::arg("linear"), py::arg("bias_slots"),
            py::arg("lr_power") = -0.5, py::arg("l1") = 0.0, py::arg("l2") = 0.0, py::arg("l2_shrinkage") = 0.0)
       .def("ftrl", &SparseLRPlan::ftrl)

@@ -13,6 +13,7 @@
 //   multi-tensor SGD / momentum / Adam (TF epsilon-hat semantics) / AdamW / Adagrad / RMSProp / FTRL   (K8, K9)
 // Every kernel is wave64-native: one wave per row/bag where rows are
 // independent, shuffles over 64 lanes, no warp-32 idioms.
+#include "auc_bin.h"
 #include "common.h"
 #include "ftrl.h"
 
@@ -578,21 +579,7 @@ __global__ void argmax_correct(const float* __restrict__ x, const int64_t* __res
 
 // Per-bin positive / negative counts of predictions in [0, 1]; bin k covers
 // thresholds [k/(nb-1) ...).  Counts accumulate across calls (streaming).
-// streaming_auc's thresholds (TF contrib.metrics): t_0 = -1e-7, t_j = j/(T-1) for
-// 0 < j < T-1 (a Python double rounded to fp32), t_{T-1} = 1 + 1e-7.  Bin k of a
-// prediction p = #{i : t_i < p} in [0, T]; the confusion counts at threshold i
-// (predicted positive <=> p > t_i) are then suffix sums over bins > i.
-__device__ __forceinline__ int tf_threshold_bin(float p, int T) {
-  if (!(p > -1e-7f)) return 0;          // (also NaN)
-  if (p > 1.f + 1e-7f) return T;
-  int lo = 1, hi = T - 1;               // first interior j with t_j >= p
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    const float t = (float)((double)mid / (double)(T - 1));
-    if (t < p) lo = mid + 1; else hi = mid;
-  }
-  return lo;                            // 1 (t_0) + (lo - 1) interior thresholds below p
-}
+// streaming_auc's thresholds and tf_threshold_bin: auc_bin.h (shared with sparse_lr.hip).
 
 // labels: nonzero = positive (TF casts to bool); pos/neg: [T + 1] bins
 __global__ void auc_hist(const float* __restrict__ pred, const float* __restrict__ label, int64_t n,

@@ -1,4 +1,4 @@
-// Reached by: one-GPU sparse LR step (csrc/bind_sparse.cpp SparseLRPlan: models/sparse_lr.py, the lr2 compat Session); tests/test_models_gpu.py, test_lowering_gpu.py, test_ftrl_gpu.py
+// Reached by: one-GPU sparse LR step and forward-only evaluation (csrc/bind_sparse.cpp SparseLRPlan: models/sparse_lr.py, the lr2 compat Session); tests/test_models_gpu.py, test_lowering_gpu.py, test_ftrl_gpu.py, test_sparse_lr_eval_gpu.py
 // lr2.py's training step on ONE GPU as two kernels:
 //
 //   py_x  = embedding_lookup_sparse(W, ids, vals, 'sum') + b      (lr2.py:383-390)
@@ -41,6 +41,25 @@
 //                   plain loads and stores (ftrl.h);
 //   slr_ftrl_clear  G[id] = 0 over the same entries (a kernel: small memset
 //                   nodes are not re-applied when a captured graph replays).
+//
+// Evaluation of the same model (lr2.py Test(), :307-315, and the closing
+// streaming_auc(sigmoid(py_x), y), :398-400,455-468) reads W and b
+// only and is two kernels, whatever the optimizer:
+//
+//   slr_eval_rows    slr_fwd's row pass without dz: the row's logit, its
+//                    sigmoid cross-entropy and p = sigmoid(z) into per-row
+//                    scratch (and, if asked, z and p into the caller's [B]
+//                    outputs); an id outside [0, F) is counted and skipped;
+//   slr_eval_reduce  one workgroup: the row losses summed in a fixed order in
+//                    fp64, every p binned over streaming_auc's thresholds
+//                    (auc_bin.h, the function auc_hist compiles) in an LDS
+//                    histogram, and both added to a device record
+//                    {loss_sum (fp64 bits), rows, bad ids, pos[T + 1],
+//                    neg[T + 1]} (int64) with plain loads and stores.  The
+//                    record accumulates across calls; `reset` (a kernel
+//                    argument, not a memset node) starts it over.  No float
+//                    atomics: two runs give the same bits.
+#include "auc_bin.h"
 #include "common.h"
 #include "ftrl.h"
 
@@ -383,6 +402,119 @@ __global__ __launch_bounds__(256) void slr_stage(const uint4* __restrict__ src, 
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) dst[i] = src[i];
 }
 
+// ------------------------------------------------------------- evaluation
+// One wave per batch row like slr_fwd.  COPY: the feed is read in place from
+// mapped pinned host memory; the labels are then left in ylab_out for
+// slr_eval_reduce (one pass over the host slot).  No barrier and no LDS here:
+// the early return of the idle waves is safe.
+template <typename ID, bool COPY = false>
+__global__ __launch_bounds__(THREADS) void slr_eval_rows(const float* __restrict__ W, long long F,
+                                                         const ID* __restrict__ ids,
+                                                         const long long* __restrict__ offsets,
+                                                         const float* __restrict__ vals,
+                                                         const float* __restrict__ labels,
+                                                         const float* __restrict__ bias, int B,
+                                                         float* __restrict__ lrow, float* __restrict__ prow,
+                                                         int* __restrict__ brow, int* __restrict__ bad,
+                                                         float* __restrict__ z_out, float* __restrict__ p_out,
+                                                         float* __restrict__ ylab_out = nullptr) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const long long s = offsets[b], e = offsets[b + 1];
+  float acc = 0.f;
+  int nbad = 0;
+  for (long long j = s + lane; j < e; j += 64) {
+    const long long id = (long long)ids[j];
+    const float v = vals != nullptr ? vals[j] : 1.f;
+    if (id < 0 || id >= F) {   // counted, skipped (slr_fwd's rule)
+      ++nbad;
+      continue;
+    }
+    acc += W[id] * v;
+  }
+  acc = wave_sum(acc);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) nbad += __shfl_xor(nbad, off, 64);
+  if (lane == 0) {
+    const float z = acc + bias[0];
+    const float y = labels[b];
+    const float p = 1.f / (1.f + __expf(-z));
+    lrow[b] = xent(z, y);
+    prow[b] = p;
+    brow[b] = nbad;
+    if (nbad != 0) atomicAdd(bad, nbad);
+    if (z_out != nullptr) z_out[b] = z;
+    if (p_out != nullptr) p_out[b] = p;
+    if constexpr (COPY) ylab_out[b] = y;
+  }
+}
+
+// rec: {loss_sum (fp64 bits), rows, bad ids, pos[T + 1], neg[T + 1]} as int64.
+// One workgroup; every thread passes every barrier (no early return).  The
+// histogram is built EBINS bins at a time (one pass for T < EBINS).
+constexpr int EBINS = 4096;   // 2 x 16 KB of LDS
+
+__global__ __launch_bounds__(THREADS) void slr_eval_reduce(const float* __restrict__ lrow,
+                                                           const float* __restrict__ prow,
+                                                           const int* __restrict__ brow,
+                                                           const float* __restrict__ labels, int B, int T, int reset,
+                                                           long long* __restrict__ rec) {
+  __shared__ unsigned int h[2][EBINS];
+  __shared__ double redl[THREADS / 64];
+  __shared__ long long redb[THREADS / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double sl = 0.0;
+  long long sb = 0;
+  for (int i = threadIdx.x; i < B; i += THREADS) {   // fixed order: thread, then lanes, then waves
+    sl += (double)lrow[i];
+    sb += brow[i];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sl += __shfl_xor(sl, off, 64);
+    sb += __shfl_xor(sb, off, 64);
+  }
+  if (lane == 0) {
+    redl[wv] = sl;
+    redb[wv] = sb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tl = 0.0;
+    long long tb = 0;
+    for (int k = 0; k < THREADS / 64; ++k) {
+      tl += redl[k];
+      tb += redb[k];
+    }
+    const double l0 = reset ? 0.0 : __longlong_as_double(rec[0]);
+    rec[0] = __double_as_longlong(l0 + tl);
+    rec[1] = (reset ? 0 : rec[1]) + B;
+    rec[2] = (reset ? 0 : rec[2]) + tb;
+  }
+  const int nb = T + 1;
+  long long* pos = rec + 3;
+  long long* neg = rec + 3 + nb;
+  for (int c0 = 0; c0 < nb; c0 += EBINS) {
+    const int cn = min(EBINS, nb - c0);
+    for (int i = threadIdx.x; i < cn; i += THREADS) {
+      h[0][i] = 0;
+      h[1][i] = 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < B; i += THREADS) {
+      const int k = tf_threshold_bin(prow[i], T) - c0;   // labels: nonzero = positive (TF casts to bool)
+      if (k >= 0 && k < cn) atomicAdd(&h[labels[i] != 0.f ? 0 : 1][k], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < cn; i += THREADS) {
+      pos[c0 + i] = (reset ? 0 : pos[c0 + i]) + (long long)h[0][i];
+      neg[c0 + i] = (reset ? 0 : neg[c0 + i]) + (long long)h[1][i];
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace slr
 }  // namespace dtfk
 
@@ -538,6 +670,31 @@ hipError_t dtfk_slr_step(float* W, long long F, const void* ids, int ids32, cons
                        bias, B, dz, lrow, bad);
     launch_apply<long long>(B, stream, W, F, id, offsets, vals, dz, lrow, lr_ptr, lr_val, bias, loss_out, gvar, gkind);
   }
+  return hipGetLastError();
+}
+
+// Forward-only evaluation: rows + reduce on `stream`.  labels_d: where the
+// reduce kernel reads the labels (device memory); direct != 0: ids / offsets /
+// vals / labels are device views of the mapped pinned feed and the rows kernel
+// copies the labels into labels_d.  rec: 3 + 2 (T + 1) int64.
+hipError_t dtfk_slr_eval(const float* W, long long F, const void* ids, int ids32, const long long* offsets,
+                         const float* vals, const float* labels, float* labels_d, int direct, const float* bias, int B,
+                         float* lrow, float* prow, int* brow, int* bad, float* z_out, float* p_out, int T, int reset,
+                         long long* rec, hipStream_t stream) {
+  using namespace dtfk::slr;
+  if (B < 1 || T < 2 || rec == nullptr || labels_d == nullptr) return hipErrorInvalidValue;
+  const int grid = (B + THREADS / 64 - 1) / (THREADS / 64);
+#define DTFK_EV(ID, COPY)                                                                                        \
+  hipLaunchKernelGGL((slr_eval_rows<ID, COPY>), dim3(grid), dim3(THREADS), 0, stream, W, F,                      \
+                     static_cast<const ID*>(ids), offsets, vals, labels, bias, B, lrow, prow, brow, bad, z_out, \
+                     p_out, labels_d)
+  if (ids32 && direct) DTFK_EV(int, true);
+  else if (ids32) DTFK_EV(int, false);
+  else if (direct) DTFK_EV(long long, true);
+  else DTFK_EV(long long, false);
+#undef DTFK_EV
+  hipLaunchKernelGGL(slr_eval_reduce, dim3(1), dim3(THREADS), 0, stream, lrow, prow, brow,
+                     direct ? static_cast<const float*>(labels_d) : labels, B, T, reset, rec);
   return hipGetLastError();
 }
 

@@ -60,6 +60,16 @@ csrc/kernels/sparse_lr.hip (bag + sigmoid-xent, LDS-aggregated scatter SGD +
 bias); with several workers, models/sparse_lr.py's sharded step (dedup,
 routing, all-to-all) on packed feeds.
 
+A run of that graph WITHOUT the train op whose fetches need only its loss,
+py_x and / or sigmoid(py_x) -- lr2.py's `Test()` fetch `[global_step,
+cross_entropy]` (:307-315) and its closing `sess.run(auc_op)` loop over
+streaming_auc(sigmoid(py_x), y) (:398-400,455-468) -- is, for one worker on one
+GPU with NumPy feeds, ONE native call on the graph's variables
+(SparseLRPlan.eval_coo: the packed feed, the forward-only kernels slr_eval_rows
++ slr_eval_reduce); loss, logits and probabilities are seeded and the metric's
+own nodes evaluate from them (`SparseLRStepPlan.eval_runs` counts them; the
+plan is built on demand, so an evaluation may precede the first train run).
+
 A run is lowered only if nothing else it fetches reads the matched
 variables or interior nodes (those would see post-update weights); anything
 unmatched -- other shapes, CPU tensors, other fetch sets -- runs eagerly as
@@ -77,7 +87,7 @@ import torch
 from .graph import Operation, Tensor
 
 _CACHE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()   # train_op -> plan | False
-_EVAL: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()    # loss / accuracy node -> weakref(MLPStepPlan)
+_EVAL: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()    # MLP loss / accuracy node -> weakref(MLPStepPlan)
 
 
 _MODS = {}
@@ -705,7 +715,7 @@ def match_sparse_lr(loss) -> Optional[SparseLRPattern]:
     idx, fids, fvals = sp_ids.indices, sp_ids.values, sp_w.values
     if not all(_placeholder(t) for t in (idx, fids, fvals, y)):
         return None
-    return SparseLRPattern(loss=loss, W=W, b=b, y=y, idx=idx, fids=fids, fvals=fvals,
+    return SparseLRPattern(loss=loss, W=W, b=b, y=y, idx=idx, fids=fids, fvals=fvals, logits=logits,
                            interior=[loss, xent, logits, e, sp_ids, sp_w])
 
 
@@ -732,6 +742,9 @@ class SparseLRStepPlan(_PlanBase):
         # DTF_SPARSE_ID_CHECK runs (0: never) and a nonzero count raises here.
         self._id_check = int(os.environ.get("DTF_SPARSE_ID_CHECK", "256"))
         self.steps = 0
+        self.eval_runs = 0            # lowered runs without the train op (run_eval)
+        self._erec = None             # run_eval's device record (csrc/bind_sparse.cpp SparseLRPlan.eval_coo)
+        self._eval_needs: Dict[tuple, Any] = {}
 
     @staticmethod
     def _feed(ctx, ph):
@@ -821,14 +834,7 @@ class SparseLRStepPlan(_PlanBase):
         fy, fi, ff, fv = (self._feed(ctx, t) for t in (p.y, p.idx, p.fids, p.fvals))
         if not all(isinstance(v, np.ndarray) for v in (fy, fi, ff, fv)):
             return False
-        if self._nplan is None:
-            from .. import _native
-
-            gv = getattr(gs_var, "value", None) if gs_var is not None else None
-            gst = gv.data if (isinstance(gv, torch.Tensor) and gv.is_cuda and gv.numel() == 1 and gv.dtype in (
-                torch.float32, torch.int64, torch.int32, torch.float64)) else None
-            self._nplan = _native.load().SparseLRPlan(table.local, p.b.value.data, gst)
-            self._nplan_gs = gst is not None
+        self._ensure_nplan(gs_var, table)
         if not self._nplan.run(fy, fi, ff, fv, float(opt._lr_value())):
             return False
         opt._steps += 1
@@ -841,6 +847,91 @@ class SparseLRStepPlan(_PlanBase):
         ctx.memo[id(p.loss)] = self._nplan.loss()   # this run's loss (a device scalar, read before the next run)
         ctx.memo[id(self.op)] = None
         self.steps += 1
+        return True
+
+    def _ensure_nplan(self, gs_var, table):
+        """The native plan on the graph's own storage; built by the first lowered
+        run, a train run or an evaluation (which may come first: step 0)."""
+        if self._nplan is None:
+            from .. import _native
+
+            gv = getattr(gs_var, "value", None) if gs_var is not None else None
+            gst = gv.data if (isinstance(gv, torch.Tensor) and gv.is_cuda and gv.numel() == 1 and gv.dtype in (
+                torch.float32, torch.int64, torch.int32, torch.float64)) else None
+            self._nplan = _native.load().SparseLRPlan(table.local, self.pat.b.value.data, gst)
+            self._nplan_gs = gst is not None
+        return self._nplan
+
+    def eval_needs(self, flat):
+        """What a run without the train op needs from this graph: a set of the
+        loss node, the logits node (py_x) and / or Sigmoid(py_x) nodes -- fetched
+        themselves or read by other fetched nodes (streaming_auc's update op);
+        empty: the fetches do not read this graph; None: they read something of
+        it that an evaluation cannot seed (the variables, another interior node)."""
+        try:
+            stack = [f for f in flat if isinstance(f, Tensor)]
+        except TypeError:
+            return None
+        key = tuple(map(id, stack))          # graph nodes only (they live as long as the graph)
+        if key in self._eval_needs:
+            return self._eval_needs[key]
+        if len(self._eval_needs) >= 64:      # a handful of fetch lists in practice: bounded all the same
+            self._eval_needs.clear()
+        p = self.pat
+        needs, seen, ok = {}, set(), True
+        while stack and ok:
+            t = stack.pop()
+            if id(t) in seen:
+                continue
+            seen.add(id(t))
+            if t is p.loss or t is p.logits or (_is(t, "Sigmoid") and len(t.inputs) == 1 and t.inputs[0] is p.logits):
+                needs[id(t)] = t
+            elif id(t) in self.blocked:
+                ok = False
+            else:
+                stack.extend(i for i in getattr(t, "inputs", ()) if isinstance(i, Tensor))
+        r = self._eval_needs[key] = (needs if ok else None)
+        return r
+
+    def run_eval(self, ctx, needs) -> bool:
+        """A run without the train op whose fetches need only the loss, py_x and /
+        or sigmoid(py_x) of this graph (lr2.py's Test() fetch [global_step,
+        cross_entropy] and its streaming_auc loop), one worker on one GPU, the
+        four feeds NumPy arrays: ONE native call (SparseLRPlan.eval_coo: the
+        feed packed into the pinned slot, the two forward-only kernels of
+        csrc/kernels/sparse_lr.hip) on the graph's own variables.  Seeds the
+        loss as the 0-d device value the eager path returns, logits and
+        probabilities as [B, 1] device tensors; everything downstream evaluates
+        from them as before.  False: not applicable, nothing done."""
+        p = self.pat
+        table = p.W.table
+        if not self._fused_env or table.hogwild is not None or table.device.type != "cuda" or \
+                _train_mod()._world_or_local().world_size != 1:
+            return False
+        fy, fi, ff, fv = (self._feed(ctx, t) for t in (p.y, p.idx, p.fids, p.fvals))
+        if not all(isinstance(v, np.ndarray) for v in (fy, fi, ff, fv)) or fy.size < 1:
+            return False
+        _resident_mod().quiesce_all()
+        nplan = self._ensure_nplan(self.info["global_step"], table)
+        dev, B = table.local.device, int(fy.size)
+        if self._erec is None:
+            self._erec = torch.zeros(3 + 2 * 3, dtype=torch.int64, device=dev)    # T = 2: the histograms go unused
+        want_z = any(t is p.logits for t in needs.values())
+        want_p = any(t is not p.logits and t is not p.loss for t in needs.values())
+        z = torch.empty(B, dtype=torch.float32, device=dev) if want_z else None
+        pr = torch.empty(B, dtype=torch.float32, device=dev) if want_p else None
+        if not nplan.eval_coo(fy, fi, ff, fv, self._erec, True, pr, z):
+            return False
+        for k, t in needs.items():
+            if t is p.loss:
+                ctx.memo[k] = (self._erec[:1].view(torch.float64) / B).float()[0]
+            elif t is p.logits:
+                ctx.memo[k] = z.view(B, 1)
+            else:
+                ctx.memo[k] = pr.view(B, 1)
+        self.eval_runs += 1
+        if self._id_check and self.eval_runs % self._id_check == 0:
+            self.check_ids()
         return True
 
     def check_ids(self):
@@ -951,21 +1042,91 @@ def _flatten(f, out: List[Any]):
     return out
 
 
-def _try_lower_eval(ctx, flat) -> None:
-    """No train op fetched: if every fetch is ONE lowered plan's loss or
-    accuracy node, run its forward-only evaluation (MLPStepPlan.run_eval)."""
-    plan = None
+def _sparse_plans(graph) -> list:
+    """The sparse-LR plans of a graph's train ops, built on demand: an
+    evaluation may come before the first train run (lr2.py's Test() at step 0).
+    The scan is cached per node count."""
+    nodes = getattr(graph, "_nodes", None)
+    if nodes is None:
+        return []
+    sc = graph.__dict__.get("_dtf_train_ops")
+    if sc is None or sc[0] != len(nodes):
+        sc = graph._dtf_train_ops = (len(nodes), [t for t in nodes if isinstance(t, Operation)
+                                                  and getattr(t, "_lowering", None) is not None
+                                                  and getattr(t, "loss", None) is not None])
+    plans = []
+    for op in sc[1]:
+        plan = _plan_of(op, graph, sparse_only=True)
+        if isinstance(plan, SparseLRStepPlan):
+            plans.append(plan)
+    return plans
+
+
+def _try_lower_eval(session, ctx, flat) -> None:
+    """No train op fetched: if the fetches belong to ONE lowered plan, run its
+    forward-only evaluation.  An MLP plan: every fetch is its loss or accuracy
+    node (MLPStepPlan.run_eval).  A sparse-LR plan: the fetches need only its
+    loss / logits / probabilities, themselves or through other nodes
+    (SparseLRStepPlan.run_eval).  Plain variables outside the plan
+    (`[global_step, cross_entropy]`, lr2.py:310) may be fetched along.  Two
+    plans, or anything a plan cannot seed: nothing is done."""
+    sparse = _sparse_plans(getattr(session, "graph", None))
+    if not _EVAL and not sparse:
+        return
+    plan, others = None, []
     for f in flat:
         try:
             ref = _EVAL.get(f)
         except TypeError:               # a fetch by name, a callable: not ours
             return
         p = ref() if ref is not None else None
-        if p is None or (plan is not None and p is not plan):
+        if p is None:
+            others.append(f)
+        elif plan is not None and p is not plan:
             return
-        plan = p
+        else:
+            plan = p
     if plan is not None:
-        plan.run_eval(ctx)
+        if all(_is_plain_var(f) and id(f) not in plan.blocked for f in others):
+            plan.run_eval(ctx)
+        return
+    hit = None
+    for sp in sparse:
+        needs = sp.eval_needs(flat)
+        if needs is None or (needs and hit is not None):
+            return
+        if needs:
+            hit = (sp, needs)
+    if hit is not None:
+        hit[0].run_eval(ctx, hit[1])
+
+
+def _plan_of(f, graph, sparse_only: bool = False):
+    """The plan of train op `f` (False: none), matched once.  sparse_only: build
+    a sparse-LR plan if the op is one, decide nothing else (None)."""
+    plan = f.__dict__.get("_dtf_plan")
+    if plan is None:
+        if sparse_only and f.__dict__.get("_dtf_not_sparse"):
+            return None                       # matched before: not a sparse-LR op
+        plan = _CACHE.get(f)
+    if plan is None:
+        loss = getattr(f, "loss", None)
+        pat = match_mlp(loss) if loss is not None and not sparse_only else None
+        plan = False
+        if pat is not None and pat.W1.value.is_cuda and {id(v) for v in f._lowering["vars"]} == \
+                {id(v) for v in (pat.W1, pat.b1, pat.W2, pat.b2)}:
+            plan = MLPStepPlan(f, pat, graph)     # (GPU kernels: CPU sessions run it op by op)
+        elif loss is not None:
+            sp = match_sparse_lr(loss)
+            if sp is not None and [id(v) for v in f._lowering["vars"]] == [id(sp.b)] and \
+                    [id(pv) for _, pv in f._lowering["sparse"]] == [id(sp.W)]:
+                plan = SparseLRStepPlan(f, sp)
+        if plan is False and sparse_only:
+            f._dtf_not_sparse = True          # the sparse match runs once; the train run decides the rest
+            return None
+        _CACHE[f] = plan
+        f._dtf_plan = plan
+    return plan
 
 
 def try_lower(session, fetches, ctx, flat=None) -> None:
@@ -975,29 +1136,13 @@ def try_lower(session, fetches, ctx, flat=None) -> None:
         return
     if flat is None:
         flat = _flatten(fetches, [])
-    if _EVAL and not any(getattr(f, "_lowering", None) is not None for f in flat):
-        _try_lower_eval(ctx, flat)
+    if not any(getattr(f, "_lowering", None) is not None for f in flat):
+        _try_lower_eval(session, ctx, flat)
         return
     for f in flat:
         if getattr(f, "_lowering", None) is None or not isinstance(f, Operation):
             continue
-        plan = f.__dict__.get("_dtf_plan")
-        if plan is None:
-            plan = _CACHE.get(f)
-        if plan is None:
-            loss = getattr(f, "loss", None)
-            pat = match_mlp(loss) if loss is not None else None
-            plan = False
-            if pat is not None and pat.W1.value.is_cuda and {id(v) for v in f._lowering["vars"]} == \
-                    {id(v) for v in (pat.W1, pat.b1, pat.W2, pat.b2)}:
-                plan = MLPStepPlan(f, pat, session.graph)     # (GPU kernels: CPU sessions run it op by op)
-            elif loss is not None:
-                sp = match_sparse_lr(loss)
-                if sp is not None and [id(v) for v in f._lowering["vars"]] == [id(sp.b)] and \
-                        [id(pv) for _, pv in f._lowering["sparse"]] == [id(sp.W)]:
-                    plan = SparseLRStepPlan(f, sp)
-            _CACHE[f] = plan
-            f._dtf_plan = plan
+        plan = _plan_of(f, session.graph)
         if plan is False or id(f) in ctx.memo:
             continue
         if plan.fetches_ok(flat) and plan.run(ctx, flat) and flat is fetches and \

@@ -80,9 +80,13 @@ class SparseLRTrainer(StaticStepMixin):
             self.b = torch.zeros(1, dtype=torch.float32, device=self.device, requires_grad=True)
         self.global_step = 0
         self._graphed = None
-        # streaming_auc's num_thresholds = auc_bins -> auc_bins + 1 histogram bins
-        self.auc_pos = torch.zeros(auc_bins + 1, dtype=torch.int64, device=self.device)
-        self.auc_neg = torch.zeros(auc_bins + 1, dtype=torch.int64, device=self.device)
+        # streaming_auc's num_thresholds = auc_bins -> auc_bins + 1 histogram bins.  The two
+        # histograms are views of one evaluation record {loss sum (fp64 bits), rows, bad ids,
+        # pos, neg}: the fused evaluation (SparseLRPlan.evaluate) adds to it in place
+        nb = auc_bins + 1
+        self._auc_rec = torch.zeros(3 + 2 * nb, dtype=torch.int64, device=self.device)
+        self.auc_pos, self.auc_neg = self._auc_rec[3:3 + nb], self._auc_rec[3 + nb:]
+        self._eval_rec = self._stream_rec = None
         # 'async': the reference's rule (lr2.py:359-396, plain GradientDescentOptimizer
         # under replica_device_setter): every worker reads W's rows from -- and
         # scatters its update into -- the owners' shared shards, b lives in a shared
@@ -162,14 +166,7 @@ class SparseLRTrainer(StaticStepMixin):
         feed: one CSR pack into a pinned slot, one staging kernel, the two step
         kernels (SparseLRPlan.run_csr); device batches straight to the kernels."""
         labels, offsets, ids, vals = batch.to(self.device) if hasattr(batch, "to") else batch
-        plan = getattr(self, "_plan", None)
-        if plan is None:
-            from .. import _native
-            plan = self._plan = _native.load().SparseLRPlan(self.W.local, self.b.data, None)
-            if self.optimizer == "ftrl":
-                from ..parallel.sharded_embedding import ftrl_kwargs
-                plan.set_ftrl(self.W.slots["Ftrl"], self.W.slots["Ftrl_1"], self.b_slots,
-                              **ftrl_kwargs(self.optimizer_hp))
+        plan = self._native_plan()
         host = _host_arrays(labels, offsets, ids, vals)
         if host is not None and plan.run_csr(*host, self.lr):
             self.global_step += 1
@@ -180,6 +177,40 @@ class SparseLRTrainer(StaticStepMixin):
                          self.lr)
         self.global_step += 1
         return loss
+
+    def _native_plan(self):
+        plan = getattr(self, "_plan", None)
+        if plan is None:
+            from .. import _native
+            plan = self._plan = _native.load().SparseLRPlan(self.W.local, self.b.data, None)
+            if self.optimizer == "ftrl":
+                from ..parallel.sharded_embedding import ftrl_kwargs
+                plan.set_ftrl(self.W.slots["Ftrl"], self.W.slots["Ftrl_1"], self.b_slots,
+                              **ftrl_kwargs(self.optimizer_hp))
+        return plan
+
+    def fused_eval_runs(self) -> int:
+        """Evaluations that ran on the one-GPU plan's forward-only kernels so far."""
+        plan = getattr(self, "_plan", None)
+        return int(plan.eval_runs()) if plan is not None else 0
+
+    def _eval_fused(self, batch, record, reset: bool, want_pred: bool = True):
+        """The batch through the plan's forward-only kernels (slr_eval_rows +
+        slr_eval_reduce): loss sum, rows and histograms are added to `record` on
+        the device.  Host batches are read in place from the packed pinned feed
+        (SparseLRPlan.eval_csr), device batches go straight to the kernels.
+        Returns the probabilities [B] (None unless asked for)."""
+        labels, offsets, ids, vals = _parts(batch, self.device)
+        plan = self._native_plan()
+        B = int(labels.numel() if torch.is_tensor(labels) else np.asarray(labels).size)
+        pred = torch.empty(B, dtype=torch.float32, device=self.device) if want_pred else None
+        host = _host_arrays(labels, offsets, ids, vals)
+        if host is not None and plan.eval_csr(*host, record, reset, pred, None):
+            return pred
+        dev = self.device
+        plan.evaluate(_dev(labels, dev, torch.float32), _dev(offsets, dev, torch.int64), _dev(ids, dev, torch.int64),
+                      None if vals is None else _dev(vals, dev, torch.float32), record, reset, pred, None)
+        return pred
 
     def _train_step_async(self, batch) -> torch.Tensor:
         """One Hogwild step: pull b, rows straight from their owners, scatter-SGD
@@ -266,16 +297,65 @@ class SparseLRTrainer(StaticStepMixin):
     def evaluate(self, batch):
         """(mean loss, probabilities) without updating (lr2.py Test(), :307-315).
         Lookups use the exact exchange: evaluation batches need no fixed shapes.
-        Collective: first applies any voided steps of the current window."""
+        Collective: first applies any voided steps of the current window.
+        One worker on a GPU: the plan's two evaluation kernels, no routing."""
+        if self._fused_ok() and _rows(batch) > 0:
+            rec = self._eval_rec
+            if rec is None:
+                rec = self._eval_rec = torch.zeros_like(self._auc_rec)
+            pred = self._eval_fused(batch, rec, True)
+            return (rec[:1].view(torch.float64) / pred.numel()).float()[0], pred
         self.sync_exchange()
         logits, labels, _ = self._forward(batch, exact=True)
         return ops.sigmoid_xent(logits, labels).detach(), torch.sigmoid(logits).reshape(-1)
 
     @torch.no_grad()
     def auc_update(self, batch):
+        if self._fused_ok() and _rows(batch) > 0:
+            self._eval_fused(batch, self._auc_rec, False, want_pred=False)
+            return
         self.sync_exchange()
         logits, labels, _ = self._forward(batch, exact=True)
         ops.auc_histogram_(torch.sigmoid(logits).reshape(-1), labels.reshape(-1), self.auc_pos, self.auc_neg)
+
+    @torch.no_grad()
+    def evaluate_stream(self, batches) -> dict:
+        """{"loss", "auc", "rows"} of an iterable of batches (this worker's): the
+        mean loss over all rows and streaming_auc's value.  On one GPU every
+        batch is added to one device record and read back once at the end; the
+        trainer's own AUC histograms (auc_update / auc) are left alone."""
+        nb = self.auc_pos.numel()
+        if self._fused_ok():
+            rec = self._stream_rec
+            if rec is None:
+                rec = self._stream_rec = torch.zeros_like(self._auc_rec)
+            first = True
+            for batch in batches:
+                if _rows(batch) > 0:
+                    self._eval_fused(batch, rec, first, want_pred=False)
+                    first = False
+            if first:
+                rec.zero_()
+            host = rec.cpu()
+            rows = int(host[1])
+            loss_sum = float(host[:1].view(torch.float64)[0])
+            pos, neg = host[3:3 + nb], host[3 + nb:]
+        else:
+            pos = torch.zeros(nb, dtype=torch.int64, device=self.device)
+            neg = torch.zeros_like(pos)
+            rows, total = 0, torch.zeros((), dtype=torch.float64, device=self.device)
+            for batch in batches:
+                n = _rows(batch)
+                if n == 0:
+                    continue
+                loss, pred = self.evaluate(batch)
+                labels = (batch.to(self.device) if hasattr(batch, "to") else batch)[0]
+                ops.auc_histogram_(pred, _dev(labels, self.device, torch.float32).reshape(-1), pos, neg)
+                total += loss.double() * n
+                rows += n
+            loss_sum = float(total)
+        return {"loss": loss_sum / rows if rows else float("nan"), "auc": ops.auc_from_histograms(pos, neg),
+                "rows": rows}
 
     def auc(self, all_workers: bool = True) -> float:
         pos, neg = self.auc_pos.clone(), self.auc_neg.clone()
@@ -324,6 +404,20 @@ def steps_per_epoch(world: World, local_batches: int) -> int:
 
 def np_sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
+
+
+def _parts(batch, dev):
+    """(labels, offsets, ids, vals) of a batch: a loader batch of NumPy arrays
+    (data/libsvm.py CSRBatch) stays on the host -- the packed feed reads it there."""
+    if not hasattr(batch, "to"):
+        return batch
+    parts = tuple(getattr(batch, k, None) for k in ("labels", "offsets", "ids", "vals"))
+    return parts if all(isinstance(x, np.ndarray) for x in parts) else batch.to(dev)
+
+
+def _rows(batch) -> int:
+    labels = batch.labels if hasattr(batch, "labels") else batch[0]
+    return int(labels.numel() if torch.is_tensor(labels) else np.asarray(labels).size)
 
 
 def _dev(t, dev, dtype):

@@ -177,7 +177,8 @@ def main(_):
         with open(FLAGS.result_json, "w") as f:
             json.dump({"auc": [float(np.asarray(v).reshape(-1)[0]) for v in auc_val] if auc_val is not None else None,
                        "loss": last, "global_step": gstep, "b": b_final, "steps": step_num, "train_s": train_s,
-                       "lowered_steps": plan.steps if plan is not None else 0}, f)
+                       "lowered_steps": plan.steps if plan is not None else 0,
+                       "lowered_evals": getattr(plan, "eval_runs", 0) if plan is not None else 0}, f)
     data_provider.close()
     server.signal_done()
     return 0

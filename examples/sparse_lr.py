@@ -131,9 +131,13 @@ def main(_argv):
     model.reset_auc()
     nt = -(-len(dp.GetTestSamples()) // FLAGS.batch_size) if FLAGS.mode == "all" else 10
     nt = sparse_lr.steps_per_epoch(world, nt)
-    for batch in dp.NextBatch("test", max_batches=nt):
-        model.auc_update(batch)
-    auc = model.auc(all_workers=True)       # (a collective: every worker finished training)
+    if world.world_size == 1:
+        # one worker: every batch is added to one device record, read back once
+        auc = model.evaluate_stream(dp.NextBatch("test", max_batches=nt))["auc"]
+    else:
+        for batch in dp.NextBatch("test", max_batches=nt):
+            model.auc_update(batch)
+        auc = model.auc(all_workers=True)   # (a collective: every worker finished training)
     model.refresh_global_step()
     log.info(f"Finish evaluate, auc: {auc}")
     if FLAGS.checkpoint:
@@ -141,7 +145,9 @@ def main(_argv):
         path = ckpt.save_sharded(FLAGS.checkpoint, local, repl, world, global_step=model.global_step)
         log.info(f"saved checkpoint {path}")
     result = {"auc": auc, "loss": last_loss, "global_step": model.global_step,
-              "b": float(model.b.detach().cpu()[0]), "steps": step, "train_s": train_s}
+              "b": float(model.b.detach().cpu()[0]), "steps": step, "train_s": train_s,
+              # evaluations that ran on the fused one-GPU plan (forward-only kernels)
+              "fused_evals": model.fused_eval_runs()}
     if FLAGS.optimizer == "ftrl":
         # rows seen = rows whose accumulator left its initial value (every worker's shard)
         seen = model.W.slots["Ftrl"] != float(model.W.opt_hp.get("initial_accumulator_value", 0.1))
