@@ -698,4 +698,16 @@ hipError_t dtfk_slr_eval(const float* W, long long F, const void* ids, int ids32
   return hipGetLastError();
 }
 
+// slr_eval_reduce alone, for another model's rows kernel (wide_deep_eval.hip):
+// per-row loss / p / bad count of B rows and the labels (device memory) into the
+// same record.  One implementation of the record for every model.
+hipError_t dtfk_eval_reduce(const float* lrow, const float* prow, const int* brow, const float* labels, int B, int T,
+                            int reset, long long* rec, hipStream_t stream) {
+  using namespace dtfk::slr;
+  if (B < 1 || T < 2 || rec == nullptr || lrow == nullptr || prow == nullptr || brow == nullptr || labels == nullptr)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(slr_eval_reduce, dim3(1), dim3(THREADS), 0, stream, lrow, prow, brow, labels, B, T, reset, rec);
+  return hipGetLastError();
+}
+
 }  // extern "C"
