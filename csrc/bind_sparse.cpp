@@ -15,14 +15,15 @@
 // both entry points from scatter-SGD to the FTRL-Proximal update (slr_fwd + the
 // three slr_ftrl_* kernels); a plan without it runs what it always ran.
 // SparseLRPlan.evaluate / eval_csr / eval_coo are the forward-only evaluation
-// (slr_eval_rows + slr_eval_reduce) of device tensors / the same host feeds:
-// packing, int32 ids and the two staging slots are the training step's
+// (slr_eval_rows + the record's reduce, eval_record.hip) of device tensors /
+// the same host feeds: packing, int32 ids and the two staging slots are the training step's
 // (submit_), the kernels read W and b only and add the batch to a device record.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <pybind11/numpy.h>
 #include <hip/hip_runtime.h>
 
+#include "eval_record_host.h"
 #include "gstep_host.h"
 
 #include <chrono>
@@ -155,20 +156,20 @@ class SparseLRPlan {
 
   // Forward-only evaluation of host feeds (run's / run_csr's arrays, packing
   // and staging slots): the batch's loss sum, row count, out-of-range ids and
-  // streaming_auc histograms are added to `record` ({loss_sum (fp64 bits), rows,
-  // bad ids, pos[T + 1], neg[T + 1]}, int64 on the device; reset: start it over).
+  // streaming_auc histograms are added to `record` (kernels/eval_record.h, on
+  // the device; reset: start it over).
   // pred / logits: optional [B] fp32 outputs (sigmoid(z), z).  Nothing of the
   // training state changes.  False: a feed run / run_csr would refuse, nothing ran.
   // The record and the outputs are checked first: a wrong record / pred / logits
   // raises whatever the feed is.
   bool eval_coo(py::array y, py::array idx, py::array ids, py::array vals, at::Tensor record, bool reset,
                 c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
-    const EvalOut o = eval_out_(y.size(), record, reset, pred, logits);
+    const EvalOut o = eval_out("SparseLRPlan", W_.get_device(), y.size(), record, reset, pred, logits);
     return coo_(y, idx, ids, vals, false, [&](const Feed& f, hipStream_t st) { eval_go_(f, o, st); });
   }
   bool eval_csr(py::array y, py::array offsets, py::array ids, py::object vals_o, at::Tensor record, bool reset,
                 c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
-    const EvalOut o = eval_out_(y.size(), record, reset, pred, logits);
+    const EvalOut o = eval_out("SparseLRPlan", W_.get_device(), y.size(), record, reset, pred, logits);
     return csr_(y, offsets, ids, vals_o, false, [&](const Feed& f, hipStream_t st) { eval_go_(f, o, st); });
   }
 
@@ -182,11 +183,6 @@ class SparseLRPlan {
     int64_t o_ids, o_off, o_val, o_lab, total;
     int B, slot;
     bool i32;
-  };
-  struct EvalOut {
-    long long* rec;
-    float *pred, *logits;
-    int T, reset;
   };
 
   template <typename Go>
@@ -339,7 +335,7 @@ class SparseLRPlan {
     const int slot = f.slot = slot_ ^ 1;
     bool ok = true;
     if (train) ensure_rows_(B);
-    else ensure_eval_(B);
+    else esc_.ensure(B, W_.options());
     at::Tensor& dvb = feed_ == 3 ? dev2_[slot] : dev_;   // overlap: one device copy per slot
     if (dvb.numel() < total) dvb = at::empty({std::max<int64_t>(total, 1 << 20)}, W_.options().dtype(at::kByte));
     hipStream_t st = c10::hip::getCurrentHIPStream().stream();
@@ -448,11 +444,11 @@ class SparseLRPlan {
 
   void eval_launch_(const void* ids, bool i32, const long long* offs, const float* vals, const float* labels,
                     bool direct, int B, const EvalOut& o, hipStream_t st) {
-    float* e = esc_.data_ptr<float>();
-    const int64_t cap = esc_.numel() / 4;   // lrow | prow | labels | bad ids per row (int)
-    hck(dtfk_slr_eval(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, e + 2 * cap,
-                      direct ? 1 : 0, bias_.data_ptr<float>(), B, e, e + cap, reinterpret_cast<int*>(e + 3 * cap),
-                      bad_.data_ptr<int>(), o.logits, o.pred, o.T, o.reset, o.rec, st),
+    // the scratch's quarters: lrow | prow | labels | bad ids per row (int)
+    hck(dtfk_slr_eval(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, esc_.part(2),
+                      direct ? 1 : 0, bias_.data_ptr<float>(), B, esc_.part(0), esc_.part(1),
+                      reinterpret_cast<int*>(esc_.part(3)), bad_.data_ptr<int>(), o.logits, o.pred, o.T, o.reset, o.rec,
+                      st),
         "SparseLRPlan: evaluation");
   }
 
@@ -461,33 +457,6 @@ class SparseLRPlan {
       dz_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
       lrow_ = at::empty({std::max<int64_t>(B, 1024)}, W_.options());
     }
-  }
-  // A larger batch gets a larger scratch; the outgrown one is kept, not freed: a
-  // captured hipGraph of an evaluation holds its pointers (both kernels of a
-  // capture use the same scratch, so a replay stays right).  16 bytes per row.
-  void ensure_eval_(int64_t B) {
-    if (esc_.numel() >= 4 * B) return;
-    if (esc_.defined()) esc_old_.push_back(esc_);
-    esc_ = at::empty({4 * std::max<int64_t>(B, 1024)}, W_.options());
-  }
-
-  // the record (3 + 2 (T + 1) int64, T >= 2) and the optional [B] outputs of an evaluation
-  EvalOut eval_out_(int64_t B, const at::Tensor& record, bool reset, const c10::optional<at::Tensor>& pred,
-                    const c10::optional<at::Tensor>& logits) const {
-    TORCH_CHECK(record.is_cuda() && record.scalar_type() == at::kLong && record.is_contiguous() &&
-                    record.get_device() == W_.get_device() && record.numel() >= 9 && (record.numel() - 3) % 2 == 0,
-                "SparseLRPlan: record must be a contiguous int64 GPU tensor of 3 + 2 (T + 1) entries, T >= 2");
-    EvalOut o{reinterpret_cast<long long*>(record.data_ptr<int64_t>()), nullptr, nullptr,
-              (int)((record.numel() - 3) / 2 - 1), reset ? 1 : 0};
-    for (int k = 0; k < 2; ++k) {
-      const c10::optional<at::Tensor>& t = k == 0 ? pred : logits;
-      if (!t.has_value()) continue;
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == B &&
-                      t->get_device() == W_.get_device(),
-                  "SparseLRPlan: pred / logits must be contiguous fp32 GPU tensors of B entries");
-      (k == 0 ? o.pred : o.logits) = t->data_ptr<float>();
-    }
-    return o;
   }
 
  public:
@@ -511,28 +480,19 @@ class SparseLRPlan {
     return loss();
   }
 
-  // Forward-only evaluation of a device batch (step's tensors and checks) into
-  // `record` (see eval_csr); W, b, the optimizer's slots, global_step, runs()
-  // and loss() are not touched.  Capturable in a hipGraph (no host read-back, no
-  // memset node): the capture holds the tensors' and the scratch's addresses.
+  // Forward-only evaluation of a device batch (step's tensors, csr_batch's
+  // checks) into `record` (see eval_csr); W, b, the optimizer's slots,
+  // global_step, runs() and loss() are not touched.  Capturable in a hipGraph (no
+  // host read-back, no memset node): the capture holds the tensors' and the
+  // scratch's addresses.
   void evaluate(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals,
                 at::Tensor record, bool reset, c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
-    TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kFloat && labels.is_contiguous(), "labels");
-    TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kLong && offsets.is_contiguous(), "offsets");
-    TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous(), "ids");
-    const int64_t B = labels.numel();
-    TORCH_CHECK(B >= 1 && B <= (1 << 30), "SparseLRPlan.evaluate: 1 <= B <= 2^30 rows");
-    TORCH_CHECK(offsets.numel() == B + 1, "SparseLRPlan.evaluate: offsets must hold B + 1 entries");
-    const float* vp = nullptr;
-    if (vals.has_value()) {
-      TORCH_CHECK(vals->is_cuda() && vals->scalar_type() == at::kFloat && vals->is_contiguous() &&
-                      vals->numel() == ids.numel(), "vals");
-      vp = vals->data_ptr<float>();
-    }
-    const EvalOut o = eval_out_(B, record, reset, pred, logits);
-    ensure_eval_(B);
-    eval_launch_(ids.data_ptr(), false, reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()), vp,
-                 labels.data_ptr<float>(), false, (int)B, o, c10::hip::getCurrentHIPStream().stream());
+    const int dev = W_.get_device();
+    const CsrBatch in = csr_batch("SparseLRPlan.evaluate", dev, labels, offsets, ids, vals);
+    const EvalOut o = eval_out("SparseLRPlan", dev, in.B, record, reset, pred, logits);
+    esc_.ensure(in.B, W_.options());
+    eval_launch_(in.ids, false, in.offsets, in.vals, in.labels, false, (int)in.B, o,
+                 c10::hip::getCurrentHIPStream().stream());
     ++eval_runs_;
   }
   int64_t eval_runs() const { return eval_runs_; }
@@ -572,7 +532,8 @@ class SparseLRPlan {
         "SparseLRPlan: step");
   }
 
-  at::Tensor W_, bias_, gstep_, loss_, bad_, dev_, dz_, lrow_, esc_;   // esc_: the evaluation's per-row scratch
+  at::Tensor W_, bias_, gstep_, loss_, bad_, dev_, dz_, lrow_;
+  EvalScratch esc_{4};   // the evaluation's per-row scratch
   at::Tensor acc_, lin_, bslots_, gsum_;   // set_ftrl: W's slots, the bias's two, the gradient accumulator
   bool ftrl_ = false;
   float hp_[4] = {-0.5f, 0.f, 0.f, 0.f};   // learning_rate_power, l1, l2, l2_shrinkage
@@ -584,7 +545,6 @@ class SparseLRPlan {
   hipEvent_t evs_[2] = {nullptr, nullptr};
   at::Tensor dev2_[2];
   std::vector<int64_t> cnt_;
-  std::vector<at::Tensor> esc_old_;   // outgrown evaluation scratch (see ensure_eval_)
   hipEvent_t ev_[2] = {nullptr, nullptr};
   bool pending_[2] = {false, false};
   GstepRef gs_;

@@ -1,6 +1,6 @@
 // The one-GPU forward-only Wide&Deep evaluation as one host call
-// (csrc/kernels/wide_deep_eval.hip wd_eval_rows + sparse_lr.hip's
-// slr_eval_reduce).  WideDeepEvalPlan holds the model's tensors themselves, not
+// (csrc/kernels/wide_deep_eval.hip wd_eval_rows + eval_record.hip's
+// eval_record_reduce).  WideDeepEvalPlan holds the model's tensors themselves, not
 // copies: training between evaluations is seen by the next one.  evaluate()
 // checks everything first and then makes its two launches on the current
 // stream: no host read-back, no memset node, so it can be captured in a
@@ -9,6 +9,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include "eval_record_host.h"
 #include "kernels/wide_deep_eval.h"
 
 #include <stdexcept>
@@ -73,55 +74,25 @@ class WideDeepEvalPlan {
     return dtfk_wd_eval_supported((int)D, (int)hidden.size() + 1, dims) == 1;
   }
 
-  // Device tensors: labels [B] / [B, 1] f32, offsets [B + 1] i64, ids [nnz] i64,
-  // vals [nnz] f32 or None.  record: 3 + 2 (T + 1) int64, T >= 2 (the sparse-LR
-  // record); reset starts it over, else the batch is added.  pred / logits: [B]
-  // f32 or None.  Every refusal raises before anything is launched.
+  // A CSR batch of device tensors (csr_batch) into `record` (eval_out: reset
+  // starts it over, else the batch is added; pred / logits: [B] f32 or None).
+  // Every refusal raises before anything is launched.
   void evaluate(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals,
                 at::Tensor record, bool reset, c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
     const int dev = emb_.get_device();
-    TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kFloat && labels.is_contiguous() &&
-                    labels.get_device() == dev, "WideDeepEvalPlan.evaluate: labels must be contiguous fp32 on the GPU");
-    TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kLong && offsets.is_contiguous() &&
-                    offsets.get_device() == dev, "WideDeepEvalPlan.evaluate: offsets must be contiguous int64 on the GPU");
-    TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous() && ids.get_device() == dev,
-                "WideDeepEvalPlan.evaluate: ids must be contiguous int64 on the GPU");
-    const int64_t B = labels.numel();
-    TORCH_CHECK(B >= 1 && B <= (1 << 30), "WideDeepEvalPlan.evaluate: 1 <= B <= 2^30 rows");
-    TORCH_CHECK(offsets.numel() == B + 1, "WideDeepEvalPlan.evaluate: offsets must hold B + 1 entries");
-    const float* vp = nullptr;
-    if (vals.has_value()) {
-      TORCH_CHECK(vals->is_cuda() && vals->scalar_type() == at::kFloat && vals->is_contiguous() &&
-                      vals->numel() == ids.numel() && vals->get_device() == dev,
-                  "WideDeepEvalPlan.evaluate: vals must be contiguous fp32 on the GPU, one per id");
-      vp = vals->data_ptr<float>();
-    }
-    TORCH_CHECK(record.is_cuda() && record.scalar_type() == at::kLong && record.is_contiguous() &&
-                    record.get_device() == dev && record.numel() >= 9 && (record.numel() - 3) % 2 == 0,
-                "WideDeepEvalPlan: record must be a contiguous int64 GPU tensor of 3 + 2 (T + 1) entries, T >= 2");
-    float* outs[2] = {nullptr, nullptr};
-    for (int k = 0; k < 2; ++k) {
-      const c10::optional<at::Tensor>& t = k == 0 ? pred : logits;
-      if (!t.has_value()) continue;
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == B &&
-                      t->get_device() == dev,
-                  "WideDeepEvalPlan: pred / logits must be contiguous fp32 GPU tensors of B entries");
-      outs[k] = t->data_ptr<float>();
-    }
-    const int T = (int)((record.numel() - 3) / 2 - 1);
-    ensure_(B);
-    float* sc = scratch_.data_ptr<float>();
-    const int64_t cap = scratch_.numel() / 3;   // lrow | prow | bad ids per row (int)
+    const CsrBatch in = csr_batch("WideDeepEvalPlan.evaluate", dev, labels, offsets, ids, vals);
+    const EvalOut o = eval_out("WideDeepEvalPlan", dev, in.B, record, reset, pred, logits);
+    scratch_.ensure(in.B, emb_.options());
     dtfk::wde::Args a{};
     a.Wt = wide_.data_ptr<float>();
     a.E = emb_.data_ptr<float>();
     a.F = (long long)emb_.size(0);
     a.D = dims_[0];
     a.mode = mode_;
-    a.ids = reinterpret_cast<const long long*>(ids.data_ptr<int64_t>());
-    a.offsets = reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>());
-    a.vals = vp;
-    a.labels = labels.data_ptr<float>();
+    a.ids = in.ids;
+    a.offsets = in.offsets;
+    a.vals = in.vals;
+    a.labels = in.labels;
     for (int l = 0; l < nl_; ++l) {
       a.W[l] = layers_[2 * l].data_ptr<float>();
       a.b[l] = layers_[2 * l + 1].data_ptr<float>();
@@ -129,16 +100,15 @@ class WideDeepEvalPlan {
     for (int l = 0; l <= nl_; ++l) a.dims[l] = dims_[l];
     a.nl = nl_;
     a.bias = bias_.data_ptr<float>();
-    a.B = (int)B;
-    a.lrow = sc;
-    a.prow = sc + cap;
-    a.brow = reinterpret_cast<int*>(sc + 2 * cap);
-    a.p_out = outs[0];
-    a.z_out = outs[1];
+    a.B = (int)in.B;
+    a.lrow = scratch_.part(0);
+    a.prow = scratch_.part(1);
+    a.brow = reinterpret_cast<int*>(scratch_.part(2));
+    a.p_out = o.pred;
+    a.z_out = o.logits;
     hipStream_t st = c10::hip::getCurrentHIPStream().stream();
     hck_(dtfk_wd_eval_rows(&a, tile_, st), "WideDeepEvalPlan: rows kernel");
-    hck_(dtfk_eval_reduce(a.lrow, a.prow, a.brow, a.labels, (int)B, T, reset ? 1 : 0,
-                          reinterpret_cast<long long*>(record.data_ptr<int64_t>()), st),
+    hck_(dtfk_eval_reduce(a.lrow, a.prow, a.brow, a.labels, a.B, o.T, o.reset, o.rec, st),
          "WideDeepEvalPlan: reduce kernel");
     ++eval_runs_;
   }
@@ -151,22 +121,15 @@ class WideDeepEvalPlan {
   }
   int tile_for(int64_t B) const { return tile_ != 0 ? tile_ : dtfk_wd_eval_tile((int)B, nl_, dims_); }
   int64_t lds_bytes(int tile) const { return dtfk_wd_eval_lds_bytes(dims_[0], nl_, dims_, tile); }
-  at::Tensor scratch() const { return scratch_; }
+  at::Tensor scratch() const { return scratch_.tensor(); }   // thirds: lrow | prow | bad ids per row (int)
 
  private:
   static void hck_(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
   }
-  // A larger batch gets a larger scratch; the outgrown one is kept alive: a
-  // captured hipGraph of an evaluation holds its pointers.  12 bytes per row.
-  void ensure_(int64_t B) {
-    if (scratch_.defined() && scratch_.numel() >= 3 * B) return;
-    if (scratch_.defined()) old_.push_back(scratch_);
-    scratch_ = at::empty({3 * std::max<int64_t>(B, 1024)}, emb_.options());
-  }
-
-  at::Tensor wide_, emb_, bias_, scratch_;
-  std::vector<at::Tensor> layers_, old_;
+  at::Tensor wide_, emb_, bias_;
+  std::vector<at::Tensor> layers_;
+  EvalScratch scratch_{3};
   int dims_[dtfk::wde::MAXL + 1] = {0, 0, 0, 0, 0};
   int nl_ = 0, mode_ = 0, tile_ = 0;
   int64_t eval_runs_ = 0;

@@ -1,6 +1,6 @@
 // streaming_auc's threshold binning, shared by every kernel that fills the
-// positive / negative histograms (ops.hip auc_hist, sparse_lr.hip
-// slr_eval_reduce): both compile this one function, so a prediction lands in
+// positive / negative histograms (ops.hip auc_hist, eval_record.hip
+// eval_record_reduce): both compile this one function, so a prediction lands in
 // the same bin whichever kernel scored it.
 #pragma once
 #include <hip/hip_runtime.h>

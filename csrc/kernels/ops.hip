@@ -579,7 +579,7 @@ __global__ void argmax_correct(const float* __restrict__ x, const int64_t* __res
 
 // Per-bin positive / negative counts of predictions in [0, 1]; bin k covers
 // thresholds [k/(nb-1) ...).  Counts accumulate across calls (streaming).
-// streaming_auc's thresholds and tf_threshold_bin: auc_bin.h (shared with sparse_lr.hip).
+// streaming_auc's thresholds and tf_threshold_bin: auc_bin.h (shared with eval_record.hip).
 
 // labels: nonzero = positive (TF casts to bool); pos/neg: [T + 1] bins
 __global__ void auc_hist(const float* __restrict__ pred, const float* __restrict__ label, int64_t n,

@@ -50,25 +50,16 @@
 //                    sigmoid cross-entropy and p = sigmoid(z) into per-row
 //                    scratch (and, if asked, z and p into the caller's [B]
 //                    outputs); an id outside [0, F) is counted and skipped;
-//   slr_eval_reduce  one workgroup: the row losses summed in a fixed order in
-//                    fp64, every p binned over streaming_auc's thresholds
-//                    (auc_bin.h, the function auc_hist compiles) in an LDS
-//                    histogram, and both added to a device record
-//                    {loss_sum (fp64 bits), rows, bad ids, pos[T + 1],
-//                    neg[T + 1]} (int64) with plain loads and stores.  The
-//                    record accumulates across calls; `reset` (a kernel
-//                    argument, not a memset node) starts it over.  No float
-//                    atomics: two runs give the same bits.
-#include "auc_bin.h"
+//   eval_record_reduce  (eval_record.hip, every model's) one workgroup: the
+//                    scratch summed into the device evaluation record.
 #include "common.h"
+#include "eval_record.h"
 #include "ftrl.h"
 
 namespace dtfk {
 namespace slr {
 
 constexpr int THREADS = 256;   // 4 waves = 4 batch rows per workgroup
-
-__device__ __forceinline__ float xent(float v, float y) { return fmaxf(v, 0.f) - v * y + log1pf(__expf(-fabsf(v))); }
 
 // COPY: ids / offsets / values / labels are read straight from the packed
 // feed in mapped pinned host memory (one pass, no staging copy in front of the
@@ -405,7 +396,7 @@ __global__ __launch_bounds__(256) void slr_stage(const uint4* __restrict__ src, 
 // ------------------------------------------------------------- evaluation
 // One wave per batch row like slr_fwd.  COPY: the feed is read in place from
 // mapped pinned host memory; the labels are then left in ylab_out for
-// slr_eval_reduce (one pass over the host slot).  No barrier and no LDS here:
+// the record's reduce (one pass over the host slot).  No barrier and no LDS here:
 // the early return of the idle waves is safe.
 template <typename ID, bool COPY = false>
 __global__ __launch_bounds__(THREADS) void slr_eval_rows(const float* __restrict__ W, long long F,
@@ -447,71 +438,6 @@ __global__ __launch_bounds__(THREADS) void slr_eval_rows(const float* __restrict
     if (z_out != nullptr) z_out[b] = z;
     if (p_out != nullptr) p_out[b] = p;
     if constexpr (COPY) ylab_out[b] = y;
-  }
-}
-
-// rec: {loss_sum (fp64 bits), rows, bad ids, pos[T + 1], neg[T + 1]} as int64.
-// One workgroup; every thread passes every barrier (no early return).  The
-// histogram is built EBINS bins at a time (one pass for T < EBINS).
-constexpr int EBINS = 4096;   // 2 x 16 KB of LDS
-
-__global__ __launch_bounds__(THREADS) void slr_eval_reduce(const float* __restrict__ lrow,
-                                                           const float* __restrict__ prow,
-                                                           const int* __restrict__ brow,
-                                                           const float* __restrict__ labels, int B, int T, int reset,
-                                                           long long* __restrict__ rec) {
-  __shared__ unsigned int h[2][EBINS];
-  __shared__ double redl[THREADS / 64];
-  __shared__ long long redb[THREADS / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double sl = 0.0;
-  long long sb = 0;
-  for (int i = threadIdx.x; i < B; i += THREADS) {   // fixed order: thread, then lanes, then waves
-    sl += (double)lrow[i];
-    sb += brow[i];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sl += __shfl_xor(sl, off, 64);
-    sb += __shfl_xor(sb, off, 64);
-  }
-  if (lane == 0) {
-    redl[wv] = sl;
-    redb[wv] = sb;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tl = 0.0;
-    long long tb = 0;
-    for (int k = 0; k < THREADS / 64; ++k) {
-      tl += redl[k];
-      tb += redb[k];
-    }
-    const double l0 = reset ? 0.0 : __longlong_as_double(rec[0]);
-    rec[0] = __double_as_longlong(l0 + tl);
-    rec[1] = (reset ? 0 : rec[1]) + B;
-    rec[2] = (reset ? 0 : rec[2]) + tb;
-  }
-  const int nb = T + 1;
-  long long* pos = rec + 3;
-  long long* neg = rec + 3 + nb;
-  for (int c0 = 0; c0 < nb; c0 += EBINS) {
-    const int cn = min(EBINS, nb - c0);
-    for (int i = threadIdx.x; i < cn; i += THREADS) {
-      h[0][i] = 0;
-      h[1][i] = 0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < B; i += THREADS) {
-      const int k = tf_threshold_bin(prow[i], T) - c0;   // labels: nonzero = positive (TF casts to bool)
-      if (k >= 0 && k < cn) atomicAdd(&h[labels[i] != 0.f ? 0 : 1][k], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < cn; i += THREADS) {
-      pos[c0 + i] = (reset ? 0 : pos[c0 + i]) + (long long)h[0][i];
-      neg[c0 + i] = (reset ? 0 : neg[c0 + i]) + (long long)h[1][i];
-    }
-    __syncthreads();
   }
 }
 
@@ -673,16 +599,20 @@ hipError_t dtfk_slr_step(float* W, long long F, const void* ids, int ids32, cons
   return hipGetLastError();
 }
 
-// Forward-only evaluation: rows + reduce on `stream`.  labels_d: where the
-// reduce kernel reads the labels (device memory); direct != 0: ids / offsets /
-// vals / labels are device views of the mapped pinned feed and the rows kernel
-// copies the labels into labels_d.  rec: 3 + 2 (T + 1) int64.
+// Forward-only evaluation: rows + the record's reduce (eval_record.hip) on
+// `stream`.  labels_d: where the reduce reads the labels (device memory);
+// direct != 0: ids / offsets / vals / labels are device views of the mapped
+// pinned feed and the rows kernel copies the labels into labels_d.  rec: the
+// record of T thresholds.  What the reduce would refuse is refused before the
+// rows kernel is launched.
 hipError_t dtfk_slr_eval(const float* W, long long F, const void* ids, int ids32, const long long* offsets,
                          const float* vals, const float* labels, float* labels_d, int direct, const float* bias, int B,
                          float* lrow, float* prow, int* brow, int* bad, float* z_out, float* p_out, int T, int reset,
                          long long* rec, hipStream_t stream) {
   using namespace dtfk::slr;
-  if (B < 1 || T < 2 || rec == nullptr || labels_d == nullptr) return hipErrorInvalidValue;
+  const float* ylab = direct ? static_cast<const float*>(labels_d) : labels;
+  if (labels_d == nullptr || !dtfk::evrec::reduce_args_ok(lrow, prow, brow, ylab, B, T, rec))
+    return hipErrorInvalidValue;
   const int grid = (B + THREADS / 64 - 1) / (THREADS / 64);
 #define DTFK_EV(ID, COPY)                                                                                        \
   hipLaunchKernelGGL((slr_eval_rows<ID, COPY>), dim3(grid), dim3(THREADS), 0, stream, W, F,                      \
@@ -693,21 +623,8 @@ hipError_t dtfk_slr_eval(const float* W, long long F, const void* ids, int ids32
   else if (direct) DTFK_EV(long long, true);
   else DTFK_EV(long long, false);
 #undef DTFK_EV
-  hipLaunchKernelGGL(slr_eval_reduce, dim3(1), dim3(THREADS), 0, stream, lrow, prow, brow,
-                     direct ? static_cast<const float*>(labels_d) : labels, B, T, reset, rec);
-  return hipGetLastError();
-}
-
-// slr_eval_reduce alone, for another model's rows kernel (wide_deep_eval.hip):
-// per-row loss / p / bad count of B rows and the labels (device memory) into the
-// same record.  One implementation of the record for every model.
-hipError_t dtfk_eval_reduce(const float* lrow, const float* prow, const int* brow, const float* labels, int B, int T,
-                            int reset, long long* rec, hipStream_t stream) {
-  using namespace dtfk::slr;
-  if (B < 1 || T < 2 || rec == nullptr || lrow == nullptr || prow == nullptr || brow == nullptr || labels == nullptr)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(slr_eval_reduce, dim3(1), dim3(THREADS), 0, stream, lrow, prow, brow, labels, B, T, reset, rec);
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : dtfk_eval_reduce(lrow, prow, brow, ylab, B, T, reset, rec, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,5 @@
-// Host interface of csrc/kernels/wide_deep_eval.hip (the forward-only Wide&Deep
-// evaluation) and of the evaluation record's reduce kernel, which lives in
-// sparse_lr.hip (slr_eval_reduce) and serves both models.
+// Host interface of csrc/kernels/wide_deep_eval.hip (the rows kernel of the
+// forward-only Wide&Deep evaluation; the reduce that follows it: eval_record.h).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -48,8 +47,4 @@ int dtfk_wd_eval_tile(int B, int nl, const int* dims);
 long long dtfk_wd_eval_lds_bytes(int D, int nl, const int* dims, int tile);
 // The rows kernel on `stream`; tile: 16, 32 or 0 (automatic).
 hipError_t dtfk_wd_eval_rows(const dtfk::wde::Args* a, int tile, hipStream_t stream);
-// slr_eval_reduce (sparse_lr.hip) on `stream`: the per-row scratch of B rows
-// into the record {loss_sum (fp64 bits), rows, bad ids, pos[T + 1], neg[T + 1]}.
-hipError_t dtfk_eval_reduce(const float* lrow, const float* prow, const int* brow, const float* labels, int B, int T,
-                            int reset, long long* rec, hipStream_t stream);
 }

@@ -31,8 +31,8 @@
 //     head    the width-1 last layer and the logit are per-row wave reductions;
 //             per-row loss, p and bad count go to scratch, z and p to the
 //             caller's [B] tensors if given.
-//   reduce  slr_eval_reduce (sparse_lr.hip, host entry dtfk_eval_reduce): the same
-//           kernel sums the scratch into the sparse-LR record.
+//   reduce  eval_record_reduce (eval_record.hip, host entry dtfk_eval_reduce): every
+//           model's reduce sums the scratch into the evaluation record.
 //
 // Ragged edges are branch-free: rows >= B are empty bags whose results are not
 // stored; the ragged last K block of the first layer (D % 16 != 0) reads clamped
@@ -72,8 +72,6 @@ constexpr int NW = THREADS / 64;
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
-
-__device__ __forceinline__ float xent(float v, float y) { return fmaxf(v, 0.f) - v * y + log1pf(__expf(-fabsf(v))); }
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ long long uni(long long v) {

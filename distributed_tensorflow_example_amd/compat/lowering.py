@@ -66,7 +66,7 @@ cross_entropy]` (:307-315) and its closing `sess.run(auc_op)` loop over
 streaming_auc(sigmoid(py_x), y) (:398-400,455-468) -- is, for one worker on one
 GPU with NumPy feeds, ONE native call on the graph's variables
 (SparseLRPlan.eval_coo: the packed feed, the forward-only kernels slr_eval_rows
-+ slr_eval_reduce); loss, logits and probabilities are seeded and the metric's
++ eval_record_reduce); loss, logits and probabilities are seeded and the metric's
 own nodes evaluate from them (`SparseLRStepPlan.eval_runs` counts them; the
 plan is built on demand, so an evaluation may precede the first train run).
 
@@ -915,16 +915,17 @@ class SparseLRStepPlan(_PlanBase):
         nplan = self._ensure_nplan(self.info["global_step"], table)
         dev, B = table.local.device, int(fy.size)
         if self._erec is None:
-            self._erec = torch.zeros(3 + 2 * 3, dtype=torch.int64, device=dev)    # T = 2: the histograms go unused
+            from ..models.eval_record import EvalRecord
+            self._erec = EvalRecord(2, dev)                                      # T = 2: the histograms go unused
         want_z = any(t is p.logits for t in needs.values())
         want_p = any(t is not p.logits and t is not p.loss for t in needs.values())
         z = torch.empty(B, dtype=torch.float32, device=dev) if want_z else None
         pr = torch.empty(B, dtype=torch.float32, device=dev) if want_p else None
-        if not nplan.eval_coo(fy, fi, ff, fv, self._erec, True, pr, z):
+        if not nplan.eval_coo(fy, fi, ff, fv, self._erec.tensor, True, pr, z):
             return False
         for k, t in needs.items():
             if t is p.loss:
-                ctx.memo[k] = (self._erec[:1].view(torch.float64) / B).float()[0]
+                ctx.memo[k] = self._erec.mean_loss(B)
             elif t is p.logits:
                 ctx.memo[k] = z.view(B, 1)
             else:

@@ -39,9 +39,10 @@ import torch
 from .. import ops
 from ..parallel.sharded_embedding import ShardedEmbedding, StaticStepMixin, lookup_shared, pad_to_capacity
 from ..parallel.world import World, get_world
+from .eval_record import StreamingEvalMixin, _dev
 
 
-class SparseLRTrainer(StaticStepMixin):
+class SparseLRTrainer(StreamingEvalMixin, StaticStepMixin):
     def __init__(self, num_features: int, lr: float, world: Optional[World] = None, seed: int = 1,
                  init_std: float = 1.0, device=None, auc_bins: int = 200, ids_capacity: Optional[int] = None,
                  rows: int = 500, peer_capacity: Optional[int] = None, update_mode: Optional[str] = None,
@@ -80,13 +81,7 @@ class SparseLRTrainer(StaticStepMixin):
             self.b = torch.zeros(1, dtype=torch.float32, device=self.device, requires_grad=True)
         self.global_step = 0
         self._graphed = None
-        # streaming_auc's num_thresholds = auc_bins -> auc_bins + 1 histogram bins.  The two
-        # histograms are views of one evaluation record {loss sum (fp64 bits), rows, bad ids,
-        # pos, neg}: the fused evaluation (SparseLRPlan.evaluate) adds to it in place
-        nb = auc_bins + 1
-        self._auc_rec = torch.zeros(3 + 2 * nb, dtype=torch.int64, device=self.device)
-        self.auc_pos, self.auc_neg = self._auc_rec[3:3 + nb], self._auc_rec[3 + nb:]
-        self._eval_rec = self._stream_rec = None
+        self._init_eval_records(auc_bins)      # auc_pos / auc_neg, streaming_auc's num_thresholds = auc_bins
         # 'async': the reference's rule (lr2.py:359-396, plain GradientDescentOptimizer
         # under replica_device_setter): every worker reads W's rows from -- and
         # scatters its update into -- the owners' shared shards, b lives in a shared
@@ -189,14 +184,13 @@ class SparseLRTrainer(StaticStepMixin):
                               **ftrl_kwargs(self.optimizer_hp))
         return plan
 
-    def fused_eval_runs(self) -> int:
-        """Evaluations that ran on the one-GPU plan's forward-only kernels so far."""
-        plan = getattr(self, "_plan", None)
-        return int(plan.eval_runs()) if plan is not None else 0
+    # ------------------------------------------------------------- evaluation
+    # (lr2.py Test(), :307-315, and its closing streaming_auc loop: the methods are StreamingEvalMixin's)
+    _eval_fused_ok = _fused_ok         # the fused evaluation applies where the fused step does
 
-    def _eval_fused(self, batch, record, reset: bool, want_pred: bool = True):
-        """The batch through the plan's forward-only kernels (slr_eval_rows +
-        slr_eval_reduce): loss sum, rows and histograms are added to `record` on
+    def _eval_into(self, batch, record, reset: bool, want_pred: bool):
+        """The batch through the plan's forward-only kernels (slr_eval_rows + the
+        record's reduce): loss sum, rows and histograms are added to `record` on
         the device.  Host batches are read in place from the packed pinned feed
         (SparseLRPlan.eval_csr), device batches go straight to the kernels.
         Returns the probabilities [B] (None unless asked for)."""
@@ -211,6 +205,10 @@ class SparseLRTrainer(StaticStepMixin):
         plan.evaluate(_dev(labels, dev, torch.float32), _dev(offsets, dev, torch.int64), _dev(ids, dev, torch.int64),
                       None if vals is None else _dev(vals, dev, torch.float32), record, reset, pred, None)
         return pred
+
+    def _eval_general(self, batch):
+        logits, labels, _ = self._forward(batch, exact=True)
+        return logits.reshape(-1), _dev(labels, self.device, torch.float32).reshape(-1), None   # (no bad-id count)
 
     def _train_step_async(self, batch) -> torch.Tensor:
         """One Hogwild step: pull b, rows straight from their owners, scatter-SGD
@@ -293,81 +291,6 @@ class SparseLRTrainer(StaticStepMixin):
             self.b -= (self.lr / ws) * gb
         return loss.detach()
 
-    @torch.no_grad()
-    def evaluate(self, batch):
-        """(mean loss, probabilities) without updating (lr2.py Test(), :307-315).
-        Lookups use the exact exchange: evaluation batches need no fixed shapes.
-        Collective: first applies any voided steps of the current window.
-        One worker on a GPU: the plan's two evaluation kernels, no routing."""
-        if self._fused_ok() and _rows(batch) > 0:
-            rec = self._eval_rec
-            if rec is None:
-                rec = self._eval_rec = torch.zeros_like(self._auc_rec)
-            pred = self._eval_fused(batch, rec, True)
-            return (rec[:1].view(torch.float64) / pred.numel()).float()[0], pred
-        self.sync_exchange()
-        logits, labels, _ = self._forward(batch, exact=True)
-        return ops.sigmoid_xent(logits, labels).detach(), torch.sigmoid(logits).reshape(-1)
-
-    @torch.no_grad()
-    def auc_update(self, batch):
-        if self._fused_ok() and _rows(batch) > 0:
-            self._eval_fused(batch, self._auc_rec, False, want_pred=False)
-            return
-        self.sync_exchange()
-        logits, labels, _ = self._forward(batch, exact=True)
-        ops.auc_histogram_(torch.sigmoid(logits).reshape(-1), labels.reshape(-1), self.auc_pos, self.auc_neg)
-
-    @torch.no_grad()
-    def evaluate_stream(self, batches) -> dict:
-        """{"loss", "auc", "rows"} of an iterable of batches (this worker's): the
-        mean loss over all rows and streaming_auc's value.  On one GPU every
-        batch is added to one device record and read back once at the end; the
-        trainer's own AUC histograms (auc_update / auc) are left alone."""
-        nb = self.auc_pos.numel()
-        if self._fused_ok():
-            rec = self._stream_rec
-            if rec is None:
-                rec = self._stream_rec = torch.zeros_like(self._auc_rec)
-            first = True
-            for batch in batches:
-                if _rows(batch) > 0:
-                    self._eval_fused(batch, rec, first, want_pred=False)
-                    first = False
-            if first:
-                rec.zero_()
-            host = rec.cpu()
-            rows = int(host[1])
-            loss_sum = float(host[:1].view(torch.float64)[0])
-            pos, neg = host[3:3 + nb], host[3 + nb:]
-        else:
-            pos = torch.zeros(nb, dtype=torch.int64, device=self.device)
-            neg = torch.zeros_like(pos)
-            rows, total = 0, torch.zeros((), dtype=torch.float64, device=self.device)
-            for batch in batches:
-                n = _rows(batch)
-                if n == 0:
-                    continue
-                loss, pred = self.evaluate(batch)
-                labels = (batch.to(self.device) if hasattr(batch, "to") else batch)[0]
-                ops.auc_histogram_(pred, _dev(labels, self.device, torch.float32).reshape(-1), pos, neg)
-                total += loss.double() * n
-                rows += n
-            loss_sum = float(total)
-        return {"loss": loss_sum / rows if rows else float("nan"), "auc": ops.auc_from_histograms(pos, neg),
-                "rows": rows}
-
-    def auc(self, all_workers: bool = True) -> float:
-        pos, neg = self.auc_pos.clone(), self.auc_neg.clone()
-        if all_workers and self.world.world_size > 1:
-            self.world.all_reduce(pos)
-            self.world.all_reduce(neg)
-        return ops.auc_from_histograms(pos, neg)
-
-    def reset_auc(self):
-        self.auc_pos.zero_()
-        self.auc_neg.zero_()
-
     # ----------------------------------------------------------------- state
     def checkpoint_tensors(self):
         """Collective: applies the voided steps of the current window first, so a
@@ -413,17 +336,6 @@ def _parts(batch, dev):
         return batch
     parts = tuple(getattr(batch, k, None) for k in ("labels", "offsets", "ids", "vals"))
     return parts if all(isinstance(x, np.ndarray) for x in parts) else batch.to(dev)
-
-
-def _rows(batch) -> int:
-    labels = batch.labels if hasattr(batch, "labels") else batch[0]
-    return int(labels.numel() if torch.is_tensor(labels) else np.asarray(labels).size)
-
-
-def _dev(t, dev, dtype):
-    if not torch.is_tensor(t):
-        t = torch.as_tensor(t)
-    return t.to(dev, dtype).contiguous()
 
 
 def _host_arrays(labels, offsets, ids, vals):

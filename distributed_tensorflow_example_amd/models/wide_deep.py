@@ -29,13 +29,17 @@ from .. import ops, optim
 from ..parallel.sharded_embedding import (ShardedEmbedding, StaticStepMixin, apply_sgd_shared, lookup_shared,
                                           pad_to_capacity)
 from ..parallel.world import World, get_world
+from .eval_record import StreamingEvalMixin, _dev
 
 
 def _no_sink_hook(p):
     """grad_sink's readiness callback: the tower's bucket is reduced after backward."""
 
 
-class WideDeep(StaticStepMixin):
+class WideDeep(StreamingEvalMixin, StaticStepMixin):
+    _eval_plan_attr = "_eval_plan"
+    _stream_reports_bad_ids = True
+
     def __init__(self, num_features: int, emb_dim: int = 64, hidden: Sequence[int] = (256, 128),
                  lr: float = 0.05, dense_lr: Optional[float] = None, dense_opt: str = "sgd", combiner: str = "sum",
                  world: Optional[World] = None, seed: int = 1, device=None, emb_std: float = 0.05,
@@ -94,13 +98,7 @@ class WideDeep(StaticStepMixin):
         self.global_step = 0
         self._graphed = None
         self._one = None
-        # streaming_auc's num_thresholds = auc_bins -> auc_bins + 1 histogram bins.  The two
-        # histograms are views of one evaluation record {loss sum (fp64 bits), rows, bad ids,
-        # pos, neg} (SparseLRTrainer's): the fused evaluation adds to it in place
-        nb = int(auc_bins) + 1
-        self._auc_rec = torch.zeros(3 + 2 * nb, dtype=torch.int64, device=self.device)
-        self.auc_pos, self.auc_neg = self._auc_rec[3:3 + nb], self._auc_rec[3 + nb:]
-        self._eval_rec = self._stream_rec = None
+        self._init_eval_records(auc_bins)      # auc_pos / auc_neg, streaming_auc's num_thresholds = auc_bins
         self._eval_plan = None
         self._eval_fused = None
 
@@ -230,6 +228,7 @@ class WideDeep(StaticStepMixin):
         return torch.sigmoid(logit).reshape(-1)
 
     # ------------------------------------------------------------- evaluation
+    # (evaluate / auc_update / evaluate_stream / auc / reset_auc: StreamingEvalMixin's, over the hooks below)
     def _eval_fused_ok(self) -> bool:
         """One worker on a GPU, no Hogwild table, a tower wd_eval_rows takes: every
         table row is local and the forward pass is one kernel
@@ -257,10 +256,6 @@ class WideDeep(StaticStepMixin):
                 self.wide.local, self.emb.local, [p.data for p in self.layers], self.bias.data, self.combiner)
         return plan
 
-    def fused_eval_runs(self) -> int:
-        """Evaluations that ran on the one-GPU plan's forward-only kernels so far."""
-        return int(self._eval_plan.eval_runs()) if self._eval_plan is not None else 0
-
     def _eval_parts(self, batch):
         labels, offsets, ids, vals = batch.to(self.device) if hasattr(batch, "to") else batch
         dev = self.device
@@ -276,86 +271,10 @@ class WideDeep(StaticStepMixin):
         self._native_eval_plan().evaluate(labels, offsets, ids, vals, record, reset, pred, None)
         return pred
 
-    @torch.no_grad()
-    def evaluate(self, batch):
-        """(mean loss, probabilities [B]) of a batch without updating anything.
-        Collective: first applies any voided steps of the current window."""
-        self.sync_exchange()
-        if self._eval_fused_ok() and _rows(batch) > 0:
-            rec = self._eval_rec
-            if rec is None:
-                rec = self._eval_rec = torch.zeros_like(self._auc_rec)
-            pred = self._eval_into(batch, rec, True, True)
-            return (rec[:1].view(torch.float64) / pred.numel()).float()[0], pred
+    def _eval_general(self, batch):
         labels, offsets, ids, vals = self._eval_parts(batch)
         logit, _ = self.forward(labels, offsets, ids, vals, exact=True)
-        return ops.sigmoid_xent(logit, labels).detach(), torch.sigmoid(logit).reshape(-1)
-
-    @torch.no_grad()
-    def auc_update(self, batch):
-        """Add the batch's predictions to the streaming-AUC histograms."""
-        self.sync_exchange()
-        if _rows(batch) == 0:
-            return
-        if self._eval_fused_ok():
-            # the record's loss sum / rows / bad ids ride along; auc_pos / auc_neg are its histogram views
-            self._eval_into(batch, self._auc_rec, False, False)
-            return
-        labels, offsets, ids, vals = self._eval_parts(batch)
-        logit, _ = self.forward(labels, offsets, ids, vals, exact=True)
-        ops.auc_histogram_(torch.sigmoid(logit).reshape(-1), labels, self.auc_pos, self.auc_neg)
-
-    @torch.no_grad()
-    def evaluate_stream(self, batches) -> dict:
-        """{"loss", "auc", "rows", "bad_ids"} of an iterable of batches (this
-        worker's): the mean loss over all rows and streaming_auc's value.  On one
-        GPU every batch is added to one device record, read back once at the end;
-        the model's own AUC histograms (auc_update / auc) are left alone."""
-        self.sync_exchange()
-        nb = self.auc_pos.numel()
-        if self._eval_fused_ok():
-            rec = self._stream_rec
-            if rec is None:
-                rec = self._stream_rec = torch.zeros_like(self._auc_rec)
-            first = True
-            for batch in batches:
-                if _rows(batch) > 0:
-                    self._eval_into(batch, rec, first, False)
-                    first = False
-            if first:
-                rec.zero_()
-            host = rec.cpu()
-            rows, bad = int(host[1]), int(host[2])
-            loss_sum = float(host[:1].view(torch.float64)[0])
-            pos, neg = host[3:3 + nb], host[3 + nb:]
-        else:
-            pos = torch.zeros(nb, dtype=torch.int64, device=self.device)
-            neg = torch.zeros_like(pos)
-            rows, bad, total = 0, 0, torch.zeros((), dtype=torch.float64, device=self.device)
-            for batch in batches:
-                if _rows(batch) == 0:
-                    continue
-                labels, offsets, ids, vals = self._eval_parts(batch)
-                logit, _ = self.forward(labels, offsets, ids, vals, exact=True)
-                logit = logit.reshape(-1)
-                total += ops.sigmoid_xent(logit, labels, reduction="none").double().sum()
-                ops.auc_histogram_(torch.sigmoid(logit), labels, pos, neg)
-                bad += int(((ids < 0) | (ids >= self.emb.num_rows)).sum())
-                rows += labels.numel()
-            loss_sum = float(total)
-        return {"loss": loss_sum / rows if rows else float("nan"), "auc": ops.auc_from_histograms(pos, neg),
-                "rows": rows, "bad_ids": bad}
-
-    def auc(self, all_workers: bool = True) -> float:
-        pos, neg = self.auc_pos.clone(), self.auc_neg.clone()
-        if all_workers and self.world.world_size > 1:
-            self.world.all_reduce(pos)
-            self.world.all_reduce(neg)
-        return ops.auc_from_histograms(pos, neg)
-
-    def reset_auc(self):
-        self.auc_pos.zero_()
-        self.auc_neg.zero_()
+        return logit.reshape(-1), labels, ids
 
     def checkpoint_tensors(self):
         """(sharded, replicated) tensors under TF names.  Collective: applies the
@@ -431,14 +350,3 @@ class WideDeep(StaticStepMixin):
                     dst.copy_(read_tensor(prefix, name).to(self.device, torch.float32).reshape(dst.shape))
         if "global_step" in idx:
             self.global_step = int(read_tensor(prefix, "global_step"))
-
-
-def _rows(batch) -> int:
-    labels = batch.labels if hasattr(batch, "labels") else batch[0]
-    return int(labels.numel() if torch.is_tensor(labels) else len(labels))
-
-
-def _dev(t, dev, dtype):
-    if not torch.is_tensor(t):
-        t = torch.as_tensor(t)
-    return t.to(dev, dtype).contiguous()

@@ -1,6 +1,7 @@
 """Float64 model of the sparse-LR forward-only evaluation, with derived error
 bounds for the fp32 kernels (csrc/kernels/sparse_lr.hip slr_eval_rows +
-slr_eval_reduce).  Not a test module: tests/test_sparse_lr_eval_*.py import it.
+eval_record.hip eval_record_reduce).  Not a test module:
+tests/test_sparse_lr_eval_*.py and test_eval_record_gpu.py import it.
 
 The model (lr2.py:383-400), per batch row r with entries (id_j, v_j):
 
@@ -59,7 +60,7 @@ additions round once each on magnitudes <= |z| (1 + |y|) + ln 2:
     lb = zb (1 + |y|) + q re(|z| + zb) + 4 u log1p(exp(-|z|))
          + 3 u (|z| (1 + |y|) + ln 2) + 2^-126.
 
-Mean loss.  slr_eval_reduce adds the fp32 row losses in fp64 (B additions,
+Mean loss.  eval_record_reduce adds the fp32 row losses in fp64 (B additions,
 each 2^-53 relative) and the host divides by the row count:
 
     mb = sum_r lb_r / B + (B + 2) 2^-53 mean |loss|      (+ u |mean| once the mean is stored as fp32).

@@ -125,6 +125,61 @@ def test_gpu_fixtures_meet_their_conditions(exact, rand):
     assert rm["pb"].max() < 1e-5 and rm["zb"].max() < 1e-4
 
 
+# ------------------------------------------------------------------ SparseLRTrainer on the CPU: the general path
+def _trainer(fx, auc_bins=200):
+    from distributed_tensorflow_example_amd.models.sparse_lr import SparseLRTrainer
+    from distributed_tensorflow_example_amd.parallel.world import World
+
+    tr = SparseLRTrainer(fx[4].size, 0.1, World(device="cpu"), seed=2, device="cpu", auc_bins=auc_bins)
+    with torch.no_grad():
+        tr.W.local.copy_(torch.from_numpy(fx[4]).reshape(-1, 1))
+        tr.b.data.fill_(float(fx[5]))
+    return tr
+
+
+def _batch(fx):
+    return tuple(None if a is None else torch.from_numpy(a) for a in fx[:4])
+
+
+def test_trainer_cpu_auc_and_stream():
+    fx, fx2 = R.random_fixture(B=257, seed=5), R.random_fixture(B=64, seed=5)      # (the same W and b)
+    assert np.array_equal(fx[4], fx2[4]) and fx[5] == fx2[5]
+    m, m2 = R.model(*fx[:6], 50), R.model(*fx2[:6], 50)
+    tr = _trainer(fx, auc_bins=50)
+    assert not tr._fused_ok() and tr.auc_pos.numel() == 51 and tr.auc_neg.numel() == 51
+    tr.auc_update(_batch(fx))
+    tr.auc_update(_batch(fx2))
+    pos, neg = tr.auc_pos.numpy().copy(), tr.auc_neg.numpy().copy()
+    R.check_histograms(pos, neg, [m, m2])
+    assert abs(tr.auc() - R.compute_auc(pos, neg)) <= 1e-6
+    st = tr.evaluate_stream([_batch(fx), _batch(fx2)])
+    assert set(st) == {"loss", "auc", "rows"} and st["rows"] == 321
+    want = (m["loss_sum"] + m2["loss_sum"]) / 321
+    assert abs(st["loss"] - want) <= (257 * m["mean_bound"] + 64 * m2["mean_bound"]) / 321
+    assert abs(st["auc"] - tr.auc()) <= 1e-6
+    assert np.array_equal(tr.auc_pos.numpy(), pos) and np.array_equal(tr.auc_neg.numpy(), neg)   # its own record
+    tr.reset_auc()
+    assert int(tr.auc_pos.sum()) == 0 and int(tr.auc_neg.sum()) == 0
+    tr.auc_update(_batch(fx))
+    R.check_histograms(tr.auc_pos.numpy(), tr.auc_neg.numpy(), m)
+    assert tr.fused_eval_runs() == 0
+
+
+def test_trainer_cpu_empty_stream_and_no_values():
+    fx = R.random_fixture(B=9, seed=1)
+    tr = _trainer(fx)
+    st = tr.evaluate_stream([])
+    assert st["rows"] == 0 and np.isnan(st["loss"]) and set(st) == {"loss", "auc", "rows"}
+    lab, off, ids, _ = _batch(fx)
+    assert tr.evaluate_stream([(lab[:0], off[:1], ids[:0], None)])["rows"] == 0                  # no rows: skipped
+    m = R.model(fx[0], fx[1], fx[2], None, fx[4], fx[5], 200)
+    loss, p = tr.evaluate((lab, off, ids, None))
+    assert loss.dim() == 0 and loss.dtype == torch.float32 and p.shape == (9,)
+    assert abs(float(loss) - m["mean"]) <= m["mean_bound"] + m["fp32_sum_extra"] + R.U * abs(m["mean"])
+    R.check_rows(m, p32=p.numpy())
+    assert tr.global_step == 0
+
+
 # ------------------------------------------------------------------ Session wiring
 def _lr2_graph(tf, F, scope):
     with tf.name_scope(scope):

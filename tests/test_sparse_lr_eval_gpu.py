@@ -17,11 +17,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import sparse_lr_eval_reference as R  # noqa: E402
+from eval_record_util import SENT, _check_sentinels, _outs, _read, _record  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = 5000
-SENT = -0x5A5A5A5A5A5A5A5
 
 
 def _plan(native, W, b, ftrl=False, gs=None):
@@ -41,25 +41,6 @@ def _dev(fx):
             None if vals is None else torch.from_numpy(vals).cuda())
 
 
-def _record(T):
-    """A record inside a sentinel-filled buffer: (whole buffer, the record view)."""
-    n = 3 + 2 * (T + 1)
-    big = torch.full((n + 2,), SENT, dtype=torch.int64, device="cuda")
-    return big, big[1:n + 1]
-
-
-def _read(rec, T):
-    h = rec.cpu()
-    nb = T + 1
-    return (float(h[:1].view(torch.float64)[0]), int(h[1]), int(h[2]), h[3:3 + nb].numpy().copy(),
-            h[3 + nb:].numpy().copy())
-
-
-def _outs(B):
-    big = torch.full((2, B + 2), float("nan"), device="cuda")
-    return big, big[0, 1:B + 1], big[1, 1:B + 1]
-
-
 def _row_losses(plan, dev_batch, T=2):
     """The kernel's loss of every row on its own: one one-row evaluation per row
     on slices of the device batch (the offsets index the whole id array), each
@@ -75,12 +56,6 @@ def _row_losses(plan, dev_batch, T=2):
     h = recs.cpu()
     assert (h[:, 1] == 1).all() and (h[:, 3:].sum(1) == 1).all()
     return h[:, 0].contiguous().view(torch.float64).numpy().copy(), h[:, 2].numpy().copy()
-
-
-def _check_sentinels(big_rec, big_out, B):
-    assert int(big_rec[0]) == SENT and int(big_rec[-1]) == SENT
-    edge = big_out[:, [0, B + 1]].cpu()
-    assert torch.isnan(edge).all() and not torch.isnan(big_out[:, 1:B + 1]).any()
 
 
 @pytest.fixture(scope="module")

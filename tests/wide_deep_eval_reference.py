@@ -1,6 +1,6 @@
 """Float64 model of the Wide&Deep forward-only evaluation, with derived error
-bounds for the fp32 kernel (csrc/kernels/wide_deep_eval.hip wd_eval_rows + the
-shared record reduce).  Not a test module: tests/test_wide_deep_eval_*.py
+bounds for the fp32 kernel (csrc/kernels/wide_deep_eval.hip wd_eval_rows +
+eval_record.hip eval_record_reduce).  Not a test module: tests/test_wide_deep_eval_*.py
 import it.  The p / loss / bin bounds, the thresholds and the histogram rule
 are tests/sparse_lr_eval_reference.py's, applied as they are once z and its
 bound zb are known; that module is imported, not changed.
