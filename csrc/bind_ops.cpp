@@ -7,6 +7,8 @@
 #include <vector>
 #include <string>
 
+#include "kernels/optim_rules.h"
+
 extern "C" {
 hipError_t dtfk_hogwild_pull(const float* shared, float* local, long long n, hipStream_t s);
 hipError_t dtfk_hogwild_sgd(float* shared, const float* g, float* local, float lr, long long n, int locking,
@@ -15,8 +17,7 @@ hipError_t dtfk_hogwild_counter(unsigned long long* counter, long long* out, lon
 hipError_t dtfk_hogwild_gather_rows(const long long* ids, int n, int D, const float* const* shards, int W, float* out,
                                    hipStream_t s);
 hipError_t dtfk_sparse_rows_apply(float* table, float* slot_a, float* slot_b, const long long* rows, const float* g,
-                                  long long n, int D, int kind, float lr, float mu, int nesterov, float rho, float eps,
-                                  float lr_power, float l1, float l2, float l2_shrinkage, const int* skip,
+                                  long long n, int D, int kind, const dtfk::OptimHyper& h, const int* skip,
                                   hipStream_t s);
 hipError_t dtfk_hogwild_scatter_sgd(const long long* ids, const float* g, int n, int D, float* const* shards, int W,
                                     float lr, int locking, hipStream_t s);
@@ -80,9 +81,8 @@ hipError_t dtfk_argmax_correct(const float* x, const int64_t* labels, int B, int
 hipError_t dtfk_auc_hist(const float* pred, const float* label, int64_t n, int nbins, unsigned long long* pos,
                          unsigned long long* neg, hipStream_t s);
 hipError_t dtfk_multi_tensor_apply(const void* tab, const void* chunks, int nchunks, int kind, int gbf,
-                                   const float* lr_ptr, float lr, float gscale, float wd, float b1, float b2,
-                                   float eps, float momentum, int nesterov, const long long* step,
-                                   const int* skip, hipStream_t s);
+                                   const float* lr_ptr, float gscale, const dtfk::OptimHyper& h,
+                                   const long long* step, const int* skip, hipStream_t s);
 hipError_t dtfk_multi_tensor_sumsq(const void* tab, const void* chunks, int nchunks, int gbf, float* out,
                                    hipStream_t s);
 int dtfk_mt_chunk();
@@ -455,10 +455,27 @@ void auc_hist(at::Tensor pred, at::Tensor label, at::Tensor pos, at::Tensor neg)
      "auc_hist");
 }
 
+// The optimizers' hyper-parameters, under the same keyword names in multi_tensor_apply and
+// sparse_rows_apply (optim/rules.py: native_kwargs fills them); each kind reads its own.
+static dtfk::OptimHyper optim_hyper(double lr, const py::kwargs& kw) {
+  size_t used = 0;
+  auto get = [&](const char* k, double dflt) {
+    if (!kw.contains(k)) return (float)dflt;
+    ++used;
+    return (float)py::cast<double>(kw[k]);
+  };
+  dtfk::OptimHyper h;
+  h.lr = (float)lr; h.momentum = get("momentum", 0.0); h.decay = get("decay", 0.9); h.eps = get("eps", 1e-10);
+  h.nesterov = get("nesterov", 0.0) != 0.f;
+  h.p = -get("lr_power", -0.5); h.l1 = get("l1", 0.0); h.l2 = get("l2", 0.0); h.shrink = get("l2_shrinkage", 0.0);
+  h.beta1 = get("beta1", 0.9); h.beta2 = get("beta2", 0.999); h.weight_decay = get("weight_decay", 0.0);
+  if (used != kw.size()) throw py::type_error("unknown optimizer hyper-parameter among the keyword arguments");
+  return h;
+}
+
 void multi_tensor_apply(at::Tensor tab, at::Tensor chunks, int kind, bool grad_bf16,
-                        c10::optional<at::Tensor> lr_t, double lr, double gscale, double wd, double b1,
-                        double b2, double eps, double momentum, bool nesterov, c10::optional<at::Tensor> step,
-                        c10::optional<at::Tensor> skip) {
+                        c10::optional<at::Tensor> lr_t, double lr, double gscale, c10::optional<at::Tensor> step,
+                        c10::optional<at::Tensor> skip, const py::kwargs& hyper) {
   gpu(tab, "table"); gpu(chunks, "chunks");
   if (tab.dim() != 2 || tab.size(1) * 8 != dtfk_tensor_rec_bytes())
     throw std::runtime_error("multi_tensor_apply: table rows must be TensorRec {p, g, m, v, n, shadow}");
@@ -467,8 +484,7 @@ void multi_tensor_apply(at::Tensor tab, at::Tensor chunks, int kind, bool grad_b
   if (skip.has_value() && (!skip->is_cuda() || skip->scalar_type() != at::kInt))
     throw std::runtime_error("multi_tensor_apply: skip must be a device int32 flag");
   ck(dtfk_multi_tensor_apply(tab.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), kind, grad_bf16 ? 1 : 0,
-                             opt_ptr<float>(lr_t), (float)lr, (float)gscale, (float)wd, (float)b1, (float)b2,
-                             (float)eps, (float)momentum, nesterov ? 1 : 0,
+                             opt_ptr<float>(lr_t), (float)gscale, optim_hyper(lr, hyper),
                              step.has_value() ? reinterpret_cast<const long long*>(step->data_ptr<int64_t>()) : nullptr,
                              skip.has_value() ? skip->data_ptr<int>() : nullptr, cs()),
      "multi_tensor_apply");
@@ -595,12 +611,10 @@ static void hogwild_scatter_sgd(at::Tensor ids, at::Tensor grads, int64_t shards
 }
 
 // Row-sparse optimizer update of a table shard (sparse_optim.hip): rows[i] >= 0
-// distinct (the owner summed the duplicates), -1 = no update.  lr_power, l1,
-// l2, l2_shrinkage: kind 6 (FTRL) only.
+// distinct (the owner summed the duplicates), -1 = no update.
 static void sparse_rows_apply(at::Tensor table, c10::optional<at::Tensor> slot_a, c10::optional<at::Tensor> slot_b,
-                              at::Tensor rows, at::Tensor g, int kind, double lr, double mu, bool nesterov,
-                              double rho, double eps, c10::optional<at::Tensor> skip, double lr_power, double l1,
-                              double l2, double l2_shrinkage) {
+                              at::Tensor rows, at::Tensor g, int kind, double lr, c10::optional<at::Tensor> skip,
+                              const py::kwargs& hyper) {
   f32c(table, "table"); i64c(rows, "rows"); f32c(g, "g");
   if (table.dim() != 2 || g.dim() != 2 || g.size(0) != rows.numel() || g.size(1) != table.size(1))
     throw std::runtime_error("sparse_rows_apply: table [R, D], g [n, D], rows [n]");
@@ -613,17 +627,13 @@ static void sparse_rows_apply(at::Tensor table, c10::optional<at::Tensor> slot_a
     throw std::runtime_error("sparse_rows_apply: skip must be a device int32 tensor");
   ck(dtfk_sparse_rows_apply(table.data_ptr<float>(), opt_ptr<float>(slot_a), opt_ptr<float>(slot_b),
                             reinterpret_cast<const long long*>(rows.data_ptr<int64_t>()), g.data_ptr<float>(),
-                            rows.numel(), (int)table.size(1), kind, (float)lr, (float)mu, nesterov ? 1 : 0,
-                            (float)rho, (float)eps, (float)lr_power, (float)l1, (float)l2, (float)l2_shrinkage,
-                            opt_ptr<int>(skip), cs()),
+                            rows.numel(), (int)table.size(1), kind, optim_hyper(lr, hyper), opt_ptr<int>(skip), cs()),
      "sparse_rows_apply");
 }
 
 void init_ops(py::module& m) {
   m.def("sparse_rows_apply", &sparse_rows_apply, py::arg("table"), py::arg("slot_a"), py::arg("slot_b"),
-        py::arg("rows"), py::arg("g"), py::arg("kind"), py::arg("lr"), py::arg("mu") = 0.0,
-        py::arg("nesterov") = false, py::arg("rho") = 0.9, py::arg("eps") = 1e-10, py::arg("skip") = py::none(),
-        py::arg("lr_power") = -0.5, py::arg("l1") = 0.0, py::arg("l2") = 0.0, py::arg("l2_shrinkage") = 0.0);
+        py::arg("rows"), py::arg("g"), py::arg("kind"), py::arg("lr"), py::arg("skip") = py::none());
   m.def("hogwild_gather_rows", &hogwild_gather_rows, py::arg("ids"), py::arg("shards"), py::arg("W"), py::arg("out"));
   m.def("hogwild_scatter_sgd", &hogwild_scatter_sgd, py::arg("ids"), py::arg("grads"), py::arg("shards"), py::arg("W"),
         py::arg("lr"), py::arg("locking"));
@@ -671,8 +681,7 @@ void init_ops(py::module& m) {
   m.def("argmax_correct", &argmax_correct);
   m.def("auc_hist", &auc_hist);
   m.def("multi_tensor_apply", &multi_tensor_apply, py::arg("tab"), py::arg("chunks"), py::arg("kind"),
-        py::arg("grad_bf16"), py::arg("lr_t"), py::arg("lr"), py::arg("gscale"), py::arg("wd"), py::arg("b1"),
-        py::arg("b2"), py::arg("eps"), py::arg("momentum"), py::arg("nesterov"), py::arg("step"),
+        py::arg("grad_bf16"), py::arg("lr_t"), py::arg("lr"), py::arg("gscale"), py::arg("step"),
         py::arg("skip") = py::none());
   m.def("multi_tensor_sumsq", &multi_tensor_sumsq);
   m.def("mt_chunk", &dtfk_mt_chunk);

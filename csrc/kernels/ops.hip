@@ -15,7 +15,7 @@
 // independent, shuffles over 64 lanes, no warp-32 idioms.
 #include "auc_bin.h"
 #include "common.h"
-#include "ftrl.h"
+#include "optim_rules.h"
 
 namespace dtfk {
 namespace ops {
@@ -614,65 +614,50 @@ __device__ __forceinline__ float ld_grad(const void* g, int64_t i, int gbf) {
   return gbf ? bf2f(reinterpret_cast<const uint16_t*>(g)[i]) : reinterpret_cast<const float*>(g)[i];
 }
 
-// kind 0: sgd, 1: momentum (use_nesterov in flags bit0), 2: adam (TF), 3: adamw,
-// 4: adagrad (TF; m = accumulator), 5: rmsprop (TF; m = mean square, v = momentum, b1 = decay),
-// 6: ftrl (TF ApplyFtrlV2, ftrl.h; m = accum, v = linear; the float arguments carry
-//    b1 = learning_rate_power, b2 = l1, eps = l2, wd = l2_shrinkage)
+// The rules, their hyper-parameters and slots: optim_rules.h (m = slot a, v = slot b).
+// Around a rule this kernel keeps what is not part of TF's op: the gradient
+// scale, weight decay (L2 on the gradient for sgd / momentum / adam, decoupled
+// for adamw) and the bf16 shadow.  `kind` is a run-time, wave-uniform branch.
 __global__ void multi_tensor_apply(const TensorRec* __restrict__ tab, const int2* __restrict__ chunks,
                                    int nchunks, int kind, int gbf, const float* __restrict__ lr_ptr,
-                                   float lr_scalar, float gscale, float wd, float b1, float b2, float eps,
-                                   float momentum, int nesterov, const long long* __restrict__ step_ptr,
+                                   float gscale, OptimHyper h, const long long* __restrict__ step_ptr,
                                    const int* __restrict__ skip) {
   const int cidx = blockIdx.x;
   if (cidx >= nchunks) return;
   if (skip != nullptr && *skip != 0) return;   // a voided step (sharded-table overflow): no update at all
   const int2 ch = chunks[cidx];
   const TensorRec t = tab[ch.x];
-  const float lr = lr_ptr ? *lr_ptr : lr_scalar;
+  const float lr = lr_ptr ? *lr_ptr : h.lr;
+  const float wd = h.weight_decay;
   float lr_t = lr;
-  if (kind == 2 || kind == 3) {
+  if (kind == OPT_ADAM || kind == OPT_ADAMW) {
     const double st = (double)(step_ptr ? *step_ptr : 1);
-    // TF AdamOptimizer: lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t), eps outside the sqrt
-    lr_t = (float)(lr * sqrt(1.0 - pow((double)b2, st)) / (1.0 - pow((double)b1, st)));
+    lr_t = (float)(lr * sqrt(1.0 - pow((double)h.beta2, st)) / (1.0 - pow((double)h.beta1, st)));
   }
   const int64_t s = (int64_t)ch.y, e = min(t.n, s + CHUNK);
   // one element: p, m, v in registers (m / v untouched by the kinds that have none)
   auto upd = [&](float& p, float g, float& m, float& v) {
     const float p0 = p;
     g *= gscale;
-    if (kind == 0) {
+    if (kind == OPT_SGD) {
       if (wd != 0.f) g += wd * p;
-      p -= lr * g;
-    } else if (kind == 1) {
+      rule_sgd(p, g, lr);
+    } else if (kind == OPT_MOMENTUM) {
       if (wd != 0.f) g += wd * p;
-      const float mv = momentum * m + g;
-      m = mv;
-      p -= lr * (nesterov ? g + momentum * mv : mv);
-    } else if (kind == 4) {
-      // TF ApplyAdagrad: accum += g^2; var -= lr * g / sqrt(accum)
-      const float acc = m + g * g;
-      m = acc;
-      p -= lr * g / sqrtf(acc);
-    } else if (kind == 5) {
-      // TF ApplyRMSProp: ms = rho ms + (1 - rho) g^2; mom = mu mom + lr g / sqrt(ms + eps); var -= mom
-      const float ms = b1 * m + (1.f - b1) * g * g;
-      const float mo = momentum * v + lr * g / sqrtf(ms + eps);
-      m = ms;
-      v = mo;
-      p -= mo;
-    } else if (kind == 6) {
-      ftrl_update(p, m, v, g, lr, -b1, b2, eps, wd);
+      rule_momentum(p, m, g, lr, h);
+    } else if (kind == OPT_ADAGRAD) {
+      rule_adagrad<false>(p, m, g, lr);
+    } else if (kind == OPT_RMSPROP) {
+      rule_rmsprop<false>(p, m, v, g, lr, h);
+    } else if (kind == OPT_FTRL) {
+      ftrl_update(p, m, v, g, lr, h.p, h.l1, h.l2, h.shrink);
     } else {
-      if (kind == 2 && wd != 0.f) g += wd * p;
-      const float mv = b1 * m + (1.f - b1) * g;
-      const float vv = b2 * v + (1.f - b2) * g * g;
-      m = mv;
-      v = vv;
-      p -= lr_t * mv / (sqrtf(vv) + eps);
-      if (kind == 3 && wd != 0.f) p -= lr * wd * p0;
+      if (kind == OPT_ADAM && wd != 0.f) g += wd * p;
+      rule_adam(p, m, v, g, lr_t, h);
+      if (kind == OPT_ADAMW && wd != 0.f) p -= lr * wd * p0;
     }
   };
-  const bool use_m = kind != 0, use_v = kind == 2 || kind == 3 || kind == 5 || kind == 6;
+  const bool use_m = uses_slot_a(kind), use_v = uses_slot_b(kind);
   // 16-byte path (4 elements per access) when every stream of this chunk is aligned:
   // the scalar loop moved 4 B per lane per access (~4.5 TB/s on BERT-base's AdamW)
   const bool vec = (s & 3) == 0 && (reinterpret_cast<uintptr_t>(t.p) & 15) == 0 &&
@@ -939,13 +924,13 @@ hipError_t dtfk_auc_hist(const float* pred, const float* label, int64_t n, int n
   return hipGetLastError();
 }
 hipError_t dtfk_multi_tensor_apply(const void* tab, const void* chunks, int nchunks, int kind, int gbf,
-                                   const float* lr_ptr, float lr, float gscale, float wd, float b1, float b2,
-                                   float eps, float momentum, int nesterov, const long long* step,
+                                   const float* lr_ptr, float gscale, const dtfk::OptimHyper& h,
+                                   const long long* step,
                                    const int* skip, hipStream_t s) {
+  if (kind == dtfk::OPT_FTRL && !dtfk::ftrl_hyper_ok(h)) return hipErrorInvalidValue;
   if (nchunks == 0) return hipSuccess;
   hipLaunchKernelGGL(multi_tensor_apply, dim3(nchunks), dim3(256), 0, s, (const TensorRec*)tab,
-                     (const int2*)chunks, nchunks, kind, gbf, lr_ptr, lr, gscale, wd, b1, b2, eps, momentum,
-                     nesterov, step, skip);
+                     (const int2*)chunks, nchunks, kind, gbf, lr_ptr, gscale, h, step, skip);
   return hipGetLastError();
 }
 hipError_t dtfk_multi_tensor_sumsq(const void* tab, const void* chunks, int nchunks, int gbf, float* out,

@@ -38,7 +38,7 @@
 //                   produces) into G[id]; the one entry in the grid that gets
 //                   something else back owns the id, what it got is the id's
 //                   summed gradient, and it updates W / accum / linear [id] with
-//                   plain loads and stores (ftrl.h);
+//                   plain loads and stores (optim_rules.h);
 //   slr_ftrl_clear  G[id] = 0 over the same entries (a kernel: small memset
 //                   nodes are not re-applied when a captured graph replays).
 //
@@ -54,7 +54,7 @@
 //                    scratch summed into the device evaluation record.
 #include "common.h"
 #include "eval_record.h"
-#include "ftrl.h"
+#include "optim_rules.h"
 
 namespace dtfk {
 namespace slr {

@@ -1,4 +1,4 @@
-// Reached by: sharded-table sparse optimizers (Wide&Deep sparse_opt=adagrad/rmsprop/momentum/ftrl); tests/test_sparse_optim_gpu.py, test_ftrl_gpu.py
+// Reached by: sharded-table sparse optimizers (Wide&Deep sparse_opt=adagrad/rmsprop/momentum/ftrl); tests/test_sparse_optim_gpu.py, test_ftrl_gpu.py, test_optim_rules_gpu.py
 // Row-sparse optimizer updates of a sharded embedding table, on its owner
 // (parallel/sharded_embedding.py: ShardedEmbedding.set_optimizer).
 //
@@ -7,66 +7,43 @@
 // then every touched row is updated on its own -- rows the batch did not touch
 // keep their value AND their slots.  The owner has already summed the
 // duplicates of a step (every rank that looked a row up sends its gradient);
-// this kernel is the per-row update:
+// this kernel is the per-row update, by the rules of optim_rules.h (slot_a,
+// slot_b as named there): kinds sgd, momentum, adagrad, rmsprop and ftrl.  Adam
+// is not row-local (m / v decay on every row): a sharded table runs the fused
+// multi-tensor Adam over its shard instead.
 //
-//   kind 0  GradientDescent  var -= lr g
-//   kind 1  Momentum         acc = mu acc + g;  var -= lr acc   (Nesterov: lr (g + mu acc))
-//   kind 4  Adagrad          acc += g^2;        var -= lr g / sqrt(acc)
-//   kind 5  RMSProp          ms = rho ms + (1-rho) g^2;  mom = mu mom + lr g / sqrt(ms + eps);  var -= mom
-//   kind 6  FTRL-Proximal    TF's SparseApplyFtrl(V2), a = accum, b = linear (ftrl.h)
-//
-// (kind numbers = optim.KINDS).  rows[i] < 0 marks an entry with no update
+// rows[i] < 0 marks an entry with no update
 // (exchange padding, the non-first copies of a duplicated row).  Rows with
 // rows[i] >= 0 are distinct, so every element has exactly one writer: plain
 // loads and stores, no atomics.  One thread per (entry, column), 4 columns
 // per thread when D % 4 == 0.  `skip` (device int32, may be null): a voided
 // step (sharded-exchange overflow) changes nothing.
 #include "common.h"
-#include "ftrl.h"
+#include "optim_rules.h"
 
 namespace dtfk {
 namespace sparse_optim {
 
-struct Hyper {
-  float lr, mu, rho, eps;
-  int kind, nesterov;
-  float p, l1, l2, shrink;   // FTRL: p = -learning_rate_power >= 0, l1, l2, l2_shrinkage
-};
+constexpr bool row_local(int kind) {
+  return kind == OPT_SGD || kind == OPT_MOMENTUM || kind == OPT_ADAGRAD || kind == OPT_RMSPROP || kind == OPT_FTRL;
+}
 
-__device__ __forceinline__ void update1(float& var, float& a, float& b, float g, const Hyper& h) {
-  switch (h.kind) {
-    case 0: var -= h.lr * g; break;
-    case 1: {
-      const float acc = h.mu * a + g;
-      a = acc;
-      var -= h.lr * (h.nesterov ? g + h.mu * acc : acc);
-      break;
-    }
-    case 4: {
-      const float acc = a + g * g;
-      a = acc;
-      var -= h.lr * g * rsqrtf(acc);
-      break;
-    }
-    case 5: {   // RMSProp, a = ms, b = mom
-      const float ms = h.rho * a + (1.f - h.rho) * g * g;
-      const float mom = h.mu * b + h.lr * g * rsqrtf(ms + h.eps);
-      a = ms;
-      b = mom;
-      var -= mom;
-      break;
-    }
-    default:   // 6: FTRL, a = accum, b = linear
-      ftrl_update(var, a, b, g, h.lr, h.p, h.l1, h.l2, h.shrink);
-      break;
+// `kind` is a run-time, wave-uniform branch
+__device__ __forceinline__ void update1(float& var, float& a, float& b, float g, int kind, const OptimHyper& h) {
+  switch (kind) {
+    case OPT_SGD: rule_sgd(var, g, h.lr); break;
+    case OPT_MOMENTUM: rule_momentum(var, a, g, h.lr, h); break;
+    case OPT_ADAGRAD: rule_adagrad<true>(var, a, g, h.lr); break;
+    case OPT_RMSPROP: rule_rmsprop<true>(var, a, b, g, h.lr, h); break;
+    default: ftrl_update(var, a, b, g, h.lr, h.p, h.l1, h.l2, h.shrink); break;   // OPT_FTRL
   }
 }
 
 template <int V>
 __global__ __launch_bounds__(256) void rows_apply(float* __restrict__ table, float* __restrict__ slot_a,
                                                   float* __restrict__ slot_b, const long long* __restrict__ rows,
-                                                  const float* __restrict__ g, long long n, int D, Hyper h,
-                                                  const int* __restrict__ skip) {
+                                                  const float* __restrict__ g, long long n, int D, int kind,
+                                                  OptimHyper h, const int* __restrict__ skip) {
   if (skip != nullptr && *skip != 0) return;
   const int dv = D / V;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,7 +63,7 @@ __global__ __launch_bounds__(256) void rows_apply(float* __restrict__ table, flo
     gg[k] = g[go + k];
   }
 #pragma unroll
-  for (int k = 0; k < V; ++k) update1(var[k], a[k], b[k], gg[k], h);
+  for (int k = 0; k < V; ++k) update1(var[k], a[k], b[k], gg[k], kind, h);
 #pragma unroll
   for (int k = 0; k < V; ++k) {
     table[o + k] = var[k];
@@ -99,22 +76,19 @@ __global__ __launch_bounds__(256) void rows_apply(float* __restrict__ table, flo
 }  // namespace dtfk
 
 extern "C" hipError_t dtfk_sparse_rows_apply(float* table, float* slot_a, float* slot_b, const long long* rows,
-                                             const float* g, long long n, int D, int kind, float lr, float mu,
-                                             int nesterov, float rho, float eps, float lr_power, float l1, float l2,
-                                             float l2_shrinkage, const int* skip, hipStream_t s) {
+                                             const float* g, long long n, int D, int kind,
+                                             const dtfk::OptimHyper& h, const int* skip, hipStream_t s) {
+  using namespace dtfk;
   using namespace dtfk::sparse_optim;
   if (n <= 0 || D <= 0) return hipSuccess;
-  if (kind != 0 && kind != 1 && kind != 4 && kind != 5 && kind != 6) return hipErrorInvalidValue;
-  if ((kind == 1 || kind == 4 || kind == 5 || kind == 6) && slot_a == nullptr) return hipErrorInvalidValue;
-  if ((kind == 5 || kind == 6) && slot_b == nullptr) return hipErrorInvalidValue;
-  if (kind == 6 && (lr_power > 0.f || l1 < 0.f || l2 < 0.f || l2_shrinkage < 0.f)) return hipErrorInvalidValue;
-  const Hyper h{lr, mu, rho, eps, kind, nesterov, -lr_power, l1, l2, l2_shrinkage};
+  if (!row_local(kind)) return hipErrorInvalidValue;
+  if (uses_slot_a(kind) && slot_a == nullptr) return hipErrorInvalidValue;
+  if (uses_slot_b(kind) && slot_b == nullptr) return hipErrorInvalidValue;
+  if (kind == OPT_FTRL && !ftrl_hyper_ok(h)) return hipErrorInvalidValue;
   const bool v4 = D % 4 == 0;
   const long long work = n * (v4 ? D / 4 : D);
   const unsigned grid = (unsigned)((work + 255) / 256);
-  if (v4)
-    hipLaunchKernelGGL(rows_apply<4>, dim3(grid), dim3(256), 0, s, table, slot_a, slot_b, rows, g, n, D, h, skip);
-  else
-    hipLaunchKernelGGL(rows_apply<1>, dim3(grid), dim3(256), 0, s, table, slot_a, slot_b, rows, g, n, D, h, skip);
+  const auto kernel = v4 ? rows_apply<4> : rows_apply<1>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, table, slot_a, slot_b, rows, g, n, D, kind, h, skip);
   return hipGetLastError();
 }

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from ..parallel import world as _worldmod
+from ..optim.rules import RULES
 from ..parallel.sharded_embedding import ShardedEmbedding
 from .graph import (GLOBAL_VARIABLES, TRAINABLE_VARIABLES, RunContext, Tensor, Variable, get_default_graph)
 
@@ -171,9 +172,8 @@ class PartitionedSlot:
         self.trainable = False
         self.initialized = True
         self.placement = pv.placement
-        # the value the optimizer gives the slot (Adagrad / FTRL accum: initial_accumulator_value, RMSProp ms: 1)
-        acc0 = float(pv.table.opt_hp.get("initial_accumulator_value", 0.1))
-        self.init = {"Adagrad": acc0, "Ftrl": acc0, "RMSProp": 1.0}.get(slot, 0.0)
+        rule = RULES[pv.table.opt_kind]      # the value the optimizer gives the slot
+        self.init = dict(zip(rule.slots, rule.slot_init(pv.table.opt_hp)))[slot]
 
     @property
     def table(self):

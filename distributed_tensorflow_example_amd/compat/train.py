@@ -340,10 +340,12 @@ class Optimizer:
     all-reduce of the gradients across workers, fused optimizer update,
     global_step += 1."""
 
-    _kind = "sgd"
-    _slot_names: Sequence[str] = ()
+    _kind = "sgd"      # the rule of optim/rules.py: slot names, their initial values, the sparse rule
 
     def __init__(self, learning_rate, use_locking=False, name=None, update_mode=None, **kw):
+        self._rule = _optim.RULES[self._kind]
+        self._slot_names: Sequence[str] = self._rule.slots
+        self._hp = {}       # the rule's hyper-parameters under TF's names (subclasses: self._rule.hp(...))
         self.learning_rate = learning_rate
         self.name = name or type(self).__name__.replace("Optimizer", "")
         self._kw = kw
@@ -356,8 +358,7 @@ class Optimizer:
         self._steps = 0
 
     def _make_fused(self, params):
-        lr = float(self._lr_value())
-        return _optim.FusedSGD(params, lr)
+        return _optim.fused(self._kind, params, self._lr_value(), **self._sparse_hp())
 
     def _lr_value(self):
         lr = self.learning_rate
@@ -397,7 +398,7 @@ class Optimizer:
         pairs = list(grads_and_vars)
         dense_pairs = [(g, v) for g, v in pairs if not _is_pv(v)]
         sparse_pairs = [(g, v) for g, v in pairs if _is_pv(v)]
-        if sparse_pairs and self._kind not in ("sgd", "momentum", "adagrad", "rmsprop", "adam", "ftrl"):
+        if sparse_pairs and not self._rule.sparse:
             raise NotImplementedError(f"{type(self).__name__}: no sparse (partitioned-variable) update rule")
         for _, pv in sparse_pairs:      # owner-side sparse rule + sharded slots (TF names var/<slot>)
             pv.table.set_optimizer(self._kind, **self._sparse_hp())
@@ -531,8 +532,8 @@ class Optimizer:
         return op
 
     def _sparse_hp(self) -> dict:
-        """Hyper-parameters of this optimizer's sparse (sharded-table) rule."""
-        return {}
+        """This optimizer's hyper-parameters (dense and sharded-table rule alike)."""
+        return dict(self._hp)
 
     def _register_pv_slots(self, pv):
         """A partitioned variable's slots: partitioned variables themselves
@@ -569,8 +570,8 @@ class Optimizer:
         """TF's non-slot optimizer variables (Adam: beta1_power / beta2_power)."""
 
     def _slot_init(self, sname: str) -> float:
-        """Initial value TF gives the slot (zeros unless the optimizer says otherwise)."""
-        return 0.0
+        """Initial value TF gives the slot."""
+        return dict(zip(self._slot_names, self._rule.slot_init(self._sparse_hp())))[sname]
 
 
 class _SlotVariable:
@@ -589,39 +590,24 @@ class _SlotVariable:
 
 
 class GradientDescentOptimizer(Optimizer):
-    def _make_fused(self, params):
-        return _optim.FusedSGD(params, self._lr_value())
+    _kind = "sgd"
 
 
 class MomentumOptimizer(Optimizer):
     _kind = "momentum"
-    _slot_names = ("Momentum",)
 
     def __init__(self, learning_rate, momentum, use_locking=False, name="Momentum", use_nesterov=False):
         super().__init__(learning_rate, use_locking, name)
-        self.momentum, self.nesterov = momentum, use_nesterov
-
-    def _make_fused(self, params):
-        return _optim.FusedMomentum(params, self._lr_value(), self.momentum, self.nesterov)
-
-    def _sparse_hp(self):
-        return {"momentum": float(self.momentum), "use_nesterov": bool(self.nesterov)}
+        self._hp = self._rule.hp({"momentum": momentum, "use_nesterov": use_nesterov})
 
 
 class AdamOptimizer(Optimizer):
     _kind = "adam"
-    _slot_names = ("Adam", "Adam_1")
 
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8, use_locking=False,
                  name="Adam"):
         super().__init__(learning_rate, use_locking, name)
-        self.beta1, self.beta2, self.epsilon = beta1, beta2, epsilon
-
-    def _make_fused(self, params):
-        return _optim.FusedAdam(params, self._lr_value(), self.beta1, self.beta2, self.epsilon)
-
-    def _sparse_hp(self):
-        return {"beta1": float(self.beta1), "beta2": float(self.beta2), "epsilon": float(self.epsilon)}
+        self._hp = self._rule.hp({"beta1": beta1, "beta2": beta2, "epsilon": epsilon})
 
     def _register_nonslot(self, dense_vars, pvs):
         # TF's non-slot accumulators beta1_power / beta2_power (= beta^(t+1)),
@@ -643,7 +629,7 @@ class AdamOptimizer(Optimizer):
         g = get_default_graph()
         steps = ([fused.step_t] if fused is not None else []) + list(getattr(self, "_pending_powers", []))
         have = {v.name: v for v in g.get_collection(GLOBAL_VARIABLES)}
-        for name, beta in (("beta1_power", self.beta1), ("beta2_power", self.beta2)):
+        for name, beta in (("beta1_power", self._hp["beta1"]), ("beta2_power", self._hp["beta2"])):
             v = have.get(name + ":0")
             if isinstance(v, _PowerVariable):
                 v.steps += [t for t in steps if all(t is not u for u in v.steps)]
@@ -700,41 +686,21 @@ class _PowerVariable:
 
 class AdagradOptimizer(Optimizer):
     _kind = "adagrad"
-    _slot_names = ("Adagrad",)
 
     def __init__(self, learning_rate, initial_accumulator_value=0.1, use_locking=False, name="Adagrad"):
         super().__init__(learning_rate, use_locking, name)
-        self.init_acc = initial_accumulator_value
-
-    def _make_fused(self, params):
-        return _optim.FusedAdagrad(params, self._lr_value(), self.init_acc)
-
-    def _sparse_hp(self):
-        return {"initial_accumulator_value": float(self.init_acc)}
-
-    def _slot_init(self, sname: str) -> float:
-        return float(self.init_acc)
+        self._hp = self._rule.hp({"initial_accumulator_value": initial_accumulator_value})
 
 
 class RMSPropOptimizer(Optimizer):
     _kind = "rmsprop"
-    _slot_names = ("RMSProp", "Momentum")
 
     def __init__(self, learning_rate, decay=0.9, momentum=0.0, epsilon=1e-10, use_locking=False,
                  centered=False, name="RMSProp"):
         super().__init__(learning_rate, use_locking, name)
         if centered:
             raise NotImplementedError("RMSPropOptimizer(centered=True) is not supported")
-        self.decay, self.mom, self.eps = decay, momentum, epsilon
-
-    def _make_fused(self, params):
-        return _optim.FusedRMSProp(params, self._lr_value(), self.decay, self.mom, self.eps)
-
-    def _sparse_hp(self):
-        return {"decay": float(self.decay), "momentum": float(self.mom), "epsilon": float(self.eps)}
-
-    def _slot_init(self, sname: str) -> float:
-        return 1.0 if sname == "RMSProp" else 0.0      # TF initialises the mean square to ones
+        self._hp = self._rule.hp({"decay": decay, "momentum": momentum, "epsilon": epsilon})
 
 
 class FtrlOptimizer(Optimizer):
@@ -748,36 +714,15 @@ class FtrlOptimizer(Optimizer):
                  l1_regularization_strength=0.0, l2_regularization_strength=0.0, use_locking=False, name="Ftrl",
                  accum_name=None, linear_name=None, l2_shrinkage_regularization_strength=0.0):
         super().__init__(learning_rate, use_locking, name)
-        if initial_accumulator_value < 0.0:
-            raise ValueError(f"initial_accumulator_value {initial_accumulator_value} needs to be positive or zero")
-        if learning_rate_power > 0.0:
-            raise ValueError(f"learning_rate_power {learning_rate_power} needs to be negative or zero")
-        if l1_regularization_strength < 0.0:
-            raise ValueError(f"l1_regularization_strength {l1_regularization_strength} needs to be positive or zero")
-        if l2_regularization_strength < 0.0:
-            raise ValueError(f"l2_regularization_strength {l2_regularization_strength} needs to be positive or zero")
-        if l2_shrinkage_regularization_strength < 0.0:
-            raise ValueError(f"l2_shrinkage_regularization_strength {l2_shrinkage_regularization_strength} needs to "
-                             "be positive or zero")
-        self.lr_power, self.init_acc = float(learning_rate_power), float(initial_accumulator_value)
-        self.l1, self.l2 = float(l1_regularization_strength), float(l2_regularization_strength)
-        self.l2_shrinkage = float(l2_shrinkage_regularization_strength)
+        self._hp = self._rule.hp({       # with TF's constructor checks
+            "learning_rate_power": learning_rate_power, "initial_accumulator_value": initial_accumulator_value,
+            "l1_regularization_strength": l1_regularization_strength,
+            "l2_regularization_strength": l2_regularization_strength,
+            "l2_shrinkage_regularization_strength": l2_shrinkage_regularization_strength})
         # TF: slot names default to the optimizer's name (<var>/Ftrl, <var>/Ftrl_1)
         accum = accum_name or self.name
         linear = linear_name or self.name
         self._slot_names = (accum, linear + "_1" if linear == accum else linear)
-
-    def _make_fused(self, params):
-        return _optim.FusedFtrl(params, self._lr_value(), self.lr_power, self.init_acc, self.l1, self.l2,
-                                self.l2_shrinkage)
-
-    def _sparse_hp(self):
-        return {"learning_rate_power": self.lr_power, "initial_accumulator_value": self.init_acc,
-                "l1_regularization_strength": self.l1, "l2_regularization_strength": self.l2,
-                "l2_shrinkage_regularization_strength": self.l2_shrinkage}
-
-    def _slot_init(self, sname: str) -> float:
-        return self.init_acc if sname == self._slot_names[0] else 0.0
 
     def _slot_alias(self, sname: str) -> Optional[str]:
         return self._slot_names[0 if sname == "Ftrl" else 1]

@@ -94,14 +94,11 @@ class SparseLRTrainer(StreamingEvalMixin, StaticStepMixin):
             if self.update_mode == "async" and self.world.world_size > 1:
                 raise NotImplementedError("asynchronous (Hogwild) updates: SGD only")
             from .. import optim
-            from ..parallel.sharded_embedding import ftrl_kwargs
             self.W.set_optimizer("ftrl", **self.optimizer_hp)     # checks the hyper-parameters as TF does
             # the bias is an FTRL variable of its own: {accum, linear} in one tensor (the fused step's layout)
-            acc0 = float(self.optimizer_hp.get("initial_accumulator_value", 0.1))
-            self.b_slots = torch.tensor([acc0, 0.0], dtype=torch.float32, device=self.device)
-            kw = ftrl_kwargs(self.optimizer_hp)
-            self._bopt = optim.FusedFtrl([self.b.data], self.lr, kw["lr_power"], acc0, kw["l1"], kw["l2"],
-                                         kw["l2_shrinkage"])
+            rule = optim.RULES["ftrl"]
+            self.b_slots = torch.tensor(rule.slot_init(self.optimizer_hp), dtype=torch.float32, device=self.device)
+            self._bopt = optim.fused("ftrl", [self.b.data], self.lr, **self.optimizer_hp)
             self._bopt.m[0], self._bopt.v[0] = self.b_slots[0:1], self.b_slots[1:2]
             self._gb = torch.zeros_like(self.b.data)
         if self.update_mode == "async" and self.world.world_size > 1:
@@ -179,9 +176,9 @@ class SparseLRTrainer(StreamingEvalMixin, StaticStepMixin):
             from .. import _native
             plan = self._plan = _native.load().SparseLRPlan(self.W.local, self.b.data, None)
             if self.optimizer == "ftrl":
-                from ..parallel.sharded_embedding import ftrl_kwargs
+                from ..optim.rules import RULES
                 plan.set_ftrl(self.W.slots["Ftrl"], self.W.slots["Ftrl_1"], self.b_slots,
-                              **ftrl_kwargs(self.optimizer_hp))
+                              **RULES["ftrl"].native_kwargs(self.optimizer_hp))
         return plan
 
     # ------------------------------------------------------------- evaluation

@@ -313,8 +313,8 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
         t = int(opt.step_t.item())
         # the integer count itself rides along (`adam_step`): the float32 powers
         # underflow (beta1 = 0.9: 0.0 after ~990 steps) and cannot pin it alone
-        return {f"{prefix}beta1_power": torch.tensor(opt.b1 ** (t + 1), dtype=torch.float32),
-                f"{prefix}beta2_power": torch.tensor(opt.b2 ** (t + 1), dtype=torch.float32),
+        return {f"{prefix}beta1_power": torch.tensor(opt.hp["beta1"] ** (t + 1), dtype=torch.float32),
+                f"{prefix}beta2_power": torch.tensor(opt.hp["beta2"] ** (t + 1), dtype=torch.float32),
                 f"{prefix}adam_step": torch.tensor(t, dtype=torch.int64)}
 
     def restore(self, prefix: str):
@@ -339,7 +339,7 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
                         steps = int(read_tensor(prefix, pre + "adam_step"))
                     elif name in idx:
                         b2 = float(read_tensor(prefix, pre + "beta2_power")) if pre + "beta2_power" in idx else None
-                        steps = adam_steps_from_powers(float(read_tensor(prefix, name)), opt.b1, b2, opt.b2)
+                        steps = adam_steps_from_powers(float(read_tensor(prefix, name)), opt.hp["beta1"], b2, opt.hp["beta2"])
                     else:
                         continue
                     opts = [opt] if opt is self.opt else [self.wide._adam, self.emb._adam]

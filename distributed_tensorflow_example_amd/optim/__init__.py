@@ -6,20 +6,11 @@ kernel over a (tensor, 4096-element chunk) work list.  Learning rate and step
 live on the device so a whole training step (including the update) can be
 captured in a hipGraph and the schedule changed without re-capture.
 
-Semantics follow TensorFlow where the reference uses it:
-  GradientDescent  p -= lr * g                         (example.py:108)
-  Momentum         m = mu*m + g; p -= lr*m (or Nesterov)
-  Adam (TF)        lr_t = lr*sqrt(1-b2^t)/(1-b1^t); p -= lr_t*m/(sqrt(v)+eps)
-                   (epsilon outside the sqrt, "epsilon hat"; model_export.py:38)
-  AdamW            decoupled weight decay (BERT recipe)
-  Adagrad (TF)     acc += g^2; p -= lr*g/sqrt(acc)      (acc starts at 0.1)
-  RMSProp (TF)     ms = rho*ms + (1-rho)*g^2; mom = mu*mom + lr*g/sqrt(ms+eps); p -= mom
-                   (ms starts at 1, as TF's RMSPropOptimizer initialises it)
-  FTRL (TF, V2)    acc' = acc + g^2; linear += g + 2*shrink*p - (acc'^q - acc^q)/lr * p;
-                   p = |linear| > l1 ? (sign(linear)*l1 - linear) / (acc'^q/lr + 2*l2) : 0
-                   (q = -learning_rate_power; acc starts at 0.1, linear at 0; exact zeros under l1)
-`grad_scale` folds the 1/N of a summed all-reduce into the update.
-CPU tensors use the same math in PyTorch (CPU/gloo configuration).
+The rules themselves (formulas, slots, hyper-parameters, kind numbers) live in
+optim/rules.py; this module wraps them with what is not part of a TF rule:
+`grad_scale` folds the 1/N of a summed all-reduce into the update, weight decay
+is L2 on the gradient (sgd, momentum, adam) or decoupled (adamw, BERT recipe).
+CPU tensors run the rules' torch form (CPU/gloo configuration).
 """
 from __future__ import annotations
 
@@ -28,10 +19,9 @@ from typing import Iterable, List, Optional
 import torch
 
 from .. import _native
+from .rules import KINDS, RULES  # noqa: F401  (KINDS: re-exported)
 
 _bump_version = torch.autograd.graph.increment_version
-
-KINDS = {"sgd": 0, "momentum": 1, "adam": 2, "adamw": 3, "adagrad": 4, "rmsprop": 5, "ftrl": 6}
 
 
 _F32_TINY = 1.1754943508222875e-38   # smallest normal float32
@@ -80,42 +70,22 @@ def _same_layout(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a.shape == b.shape and all(x == y for x, y, n in zip(a.stride(), b.stride(), a.shape) if n > 1)
 
 
-def ftrl_torch_(var, acc, lin, g, lr, lr_power=-0.5, l1=0.0, l2=0.0, l2_shrinkage=0.0):
-    """TF's ApplyFtrl(V2) in place on float32 tensors (csrc/kernels/ftrl.h, same
-    operation order); g: the duplicate-summed, unshrunk gradient."""
-    p = -float(lr_power)
-    pw = (lambda a: a.sqrt()) if p == 0.5 else ((lambda a: torch.ones_like(a)) if p == 0.0 else (lambda a: a.pow(p)))
-    gs = g + 2.0 * l2_shrinkage * var if l2_shrinkage != 0.0 else g
-    an = acc + g * g
-    pn = pw(an)
-    sigma = (pn - pw(acc)) / lr
-    l = lin + gs - sigma * var
-    quad = pn / lr + 2.0 * l2
-    step = (torch.sign(l) * l1 - l) / quad
-    var.copy_(torch.where(l.abs() > l1, step, torch.zeros_like(step)))   # a select: the untaken 0 / 0 never lands
-    acc.copy_(an)
-    lin.copy_(l)
-
-
 class _FusedBase:
     kind = "sgd"
 
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, weight_decay: float = 0.0,
-                 beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, momentum: float = 0.0,
-                 nesterov: bool = False):
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, weight_decay: float = 0.0, **hp):
+        """hp: the rule's hyper-parameters under TF's names (rules.py)."""
         self.params: List[torch.Tensor] = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
         self.device = self.params[0].device
-        self.wd, self.b1, self.b2, self.eps = weight_decay, beta1, beta2, eps
-        self.momentum, self.nesterov = momentum, nesterov
+        self.rule = RULES[self.kind]
+        self.wd, self.hp = weight_decay, self.rule.hp(hp)
         self.lr_t = torch.tensor([float(lr)], dtype=torch.float32, device=self.device)
         self.step_t = torch.zeros(1, dtype=torch.int64, device=self.device)
-        need_m = self.kind in ("momentum", "adam", "adamw", "adagrad", "rmsprop", "ftrl")
-        need_v = self.kind in ("adam", "adamw", "rmsprop", "ftrl")
-        m0 = {"adagrad": self._init_acc(), "rmsprop": 1.0, "ftrl": self._init_acc()}.get(self.kind, 0.0)
-        self.m = [torch.full_like(p, m0, dtype=torch.float32) if need_m else None for p in self.params]
-        self.v = [torch.zeros_like(p, dtype=torch.float32) if need_v else None for p in self.params]
+        init = self.rule.slot_init(self.hp) + (None, None)
+        self.m, self.v = ([torch.full_like(p, v0, dtype=torch.float32) if v0 is not None else None
+                           for p in self.params] for v0 in init[:2])
         self._tab_key = None
         self._tab = None
         self._chunks = None
@@ -130,9 +100,6 @@ class _FusedBase:
         with torch.no_grad():
             shadow.copy_(param)
         self._tab_key = None
-
-    def _init_acc(self) -> float:
-        return 0.0
 
     # ------------------------------------------------------------------ state
     @property
@@ -215,10 +182,9 @@ class _FusedBase:
             grads = [g.float() for g in grads]
         gbf = grads[0].dtype == torch.bfloat16
         tab, chunks = self._table(grads)
-        _native.load().multi_tensor_apply(tab, chunks, KINDS[self.kind], gbf, self.lr_t, 0.0,
-                                          float(grad_scale), self.wd, self.b1, self.b2, self.eps,
-                                          self.momentum, self.nesterov, self.step_t,
-                                          None if skip is None else skip.reshape(-1)[:1].to(torch.int32))
+        _native.load().multi_tensor_apply(tab, chunks, self.rule.kind, gbf, self.lr_t, 0.0, float(grad_scale),
+                                          self.step_t, None if skip is None else skip.reshape(-1)[:1].to(torch.int32),
+                                          weight_decay=self.wd, **self.rule.native_kwargs(self.hp))
         # the kernel rewrote the bf16 shadows in place: bump their version counters as
         # an in-place torch op would (caches keyed on them, e.g. ops/conv.py's flipped
         # filters, see the change; a graph still holding an old shadow raises as usual)
@@ -237,39 +203,12 @@ class _FusedBase:
         t = int(self.step_t.item())
         for i, (p, g) in enumerate(zip(self.params, grads)):
             g = g.float() * gs
-            if self.kind == "sgd":
-                if self.wd:
-                    g = g + self.wd * p
-                p.sub_(lr * g)
-            elif self.kind == "momentum":
-                if self.wd:
-                    g = g + self.wd * p
-                m = self.m[i]
-                m.mul_(self.momentum).add_(g)
-                p.sub_(lr * (g + self.momentum * m if self.nesterov else m))
-            elif self.kind == "adagrad":
-                m = self.m[i]
-                m.add_(g * g)
-                p.sub_(lr * g / m.sqrt())
-            elif self.kind == "rmsprop":
-                m, v = self.m[i], self.v[i]
-                m.mul_(self.b1).add_((1 - self.b1) * g * g)
-                v.mul_(self.momentum).add_(lr * g / (m + self.eps).sqrt())
-                p.sub_(v)
-            elif self.kind == "ftrl":
-                # as the kernel reads them: b1 = learning_rate_power, b2 = l1, eps = l2, wd = l2_shrinkage
-                ftrl_torch_(p, self.m[i], self.v[i], g, lr, self.b1, self.b2, self.eps, self.wd)
-            else:
-                if self.kind == "adam" and self.wd:
-                    g = g + self.wd * p
-                m, v = self.m[i], self.v[i]
-                m.mul_(self.b1).add_((1 - self.b1) * g)
-                v.mul_(self.b2).add_((1 - self.b2) * g * g)
-                lr_t = lr * (1 - self.b2 ** t) ** 0.5 / (1 - self.b1 ** t)
-                p0 = p.clone() if self.kind == "adamw" else None
-                p.sub_(lr_t * m / (v.sqrt() + self.eps))
-                if self.kind == "adamw" and self.wd:
-                    p.sub_(lr * self.wd * p0)
+            if self.wd and self.kind in ("sgd", "momentum", "adam"):
+                g = g + self.wd * p
+            p0 = p.clone() if self.kind == "adamw" and self.wd else None
+            self.rule.update_(p, self.m[i], self.v[i], g, lr, self.hp, fast_rsqrt=False, t=t)
+            if p0 is not None:
+                p.sub_(lr * self.wd * p0)
 
 
 class FusedSGD(_FusedBase):
@@ -283,7 +222,7 @@ class FusedMomentum(_FusedBase):
     kind = "momentum"
 
     def __init__(self, params, lr, momentum=0.9, nesterov=False, weight_decay=0.0):
-        super().__init__(params, lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov)
+        super().__init__(params, lr, weight_decay=weight_decay, momentum=momentum, use_nesterov=nesterov)
 
 
 class FusedAdam(_FusedBase):
@@ -292,14 +231,14 @@ class FusedAdam(_FusedBase):
     kind = "adam"
 
     def __init__(self, params, lr=0.001, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
-        super().__init__(params, lr, weight_decay=weight_decay, beta1=beta1, beta2=beta2, eps=eps)
+        super().__init__(params, lr, weight_decay=weight_decay, beta1=beta1, beta2=beta2, epsilon=eps)
 
 
 class FusedAdamW(_FusedBase):
     kind = "adamw"
 
     def __init__(self, params, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.01):
-        super().__init__(params, lr, weight_decay=weight_decay, beta1=beta1, beta2=beta2, eps=eps)
+        super().__init__(params, lr, weight_decay=weight_decay, beta1=beta1, beta2=beta2, epsilon=eps)
 
 
 class FusedAdagrad(_FusedBase):
@@ -308,11 +247,7 @@ class FusedAdagrad(_FusedBase):
     kind = "adagrad"
 
     def __init__(self, params, lr, initial_accumulator_value=0.1):
-        self._acc0 = float(initial_accumulator_value)
-        super().__init__(params, lr)
-
-    def _init_acc(self) -> float:
-        return self._acc0
+        super().__init__(params, lr, initial_accumulator_value=initial_accumulator_value)
 
 
 class FusedRMSProp(_FusedBase):
@@ -321,31 +256,30 @@ class FusedRMSProp(_FusedBase):
     kind = "rmsprop"
 
     def __init__(self, params, lr, decay=0.9, momentum=0.0, epsilon=1e-10):
-        super().__init__(params, lr, beta1=decay, eps=epsilon, momentum=momentum)
+        super().__init__(params, lr, decay=decay, momentum=momentum, epsilon=epsilon)
 
 
 class FusedFtrl(_FusedBase):
     """TF FtrlOptimizer (ApplyFtrlV2): m = accum (starts at initial_accumulator_value),
-    v = linear (starts at 0).  The multi-tensor kernel takes its hyper-parameters in
-    the float arguments the other kinds use: b1 = learning_rate_power, b2 = l1,
-    eps = l2, weight_decay = l2_shrinkage."""
+    v = linear (starts at 0)."""
 
     kind = "ftrl"
 
     def __init__(self, params, lr, learning_rate_power=-0.5, initial_accumulator_value=0.1, l1=0.0, l2=0.0,
                  l2_shrinkage=0.0):
-        if initial_accumulator_value < 0.0:
-            raise ValueError("initial_accumulator_value needs to be positive or zero")
-        if learning_rate_power > 0.0:
-            raise ValueError("learning_rate_power needs to be negative or zero")
-        if l1 < 0.0 or l2 < 0.0 or l2_shrinkage < 0.0:
-            raise ValueError("l1, l2 and l2_shrinkage need to be positive or zero")
-        self._acc0 = float(initial_accumulator_value)
-        super().__init__(params, lr, weight_decay=float(l2_shrinkage), beta1=float(learning_rate_power),
-                         beta2=float(l1), eps=float(l2))
+        super().__init__(params, lr, learning_rate_power=learning_rate_power,
+                         initial_accumulator_value=initial_accumulator_value, l1_regularization_strength=l1,
+                         l2_regularization_strength=l2, l2_shrinkage_regularization_strength=l2_shrinkage)
 
-    def _init_acc(self) -> float:
-        return self._acc0
+
+FUSED = {c.kind: c for c in (FusedSGD, FusedMomentum, FusedAdam, FusedAdamW, FusedAdagrad, FusedRMSProp, FusedFtrl)}
+
+
+def fused(kind: str, params, lr: float, **hp) -> _FusedBase:
+    """The fused optimizer of rule `kind`, its hyper-parameters under TF's names (rules.py)."""
+    opt = FUSED[kind].__new__(FUSED[kind])
+    _FusedBase.__init__(opt, params, lr, **hp)
+    return opt
 
 
 def global_grad_norm(grads: List[torch.Tensor]) -> torch.Tensor:

@@ -46,6 +46,7 @@ from typing import Optional
 import torch
 
 from .. import ops
+from ..optim.rules import RULES
 from .world import World, get_world
 
 
@@ -299,48 +300,30 @@ class ShardedEmbedding:
     # ------------------------------------------------------------------ optimizer
     def set_optimizer(self, kind: str = "sgd", **hp):
         """The owner-side update of this table's sparse gradients, TensorFlow's
-        sparse-apply semantics (duplicates summed, then each touched row):
-
-          sgd       var -= lr g                                  (ScatterSub / SparseApplyGradientDescent)
-          momentum  acc = mu acc + g; var -= lr acc (nesterov)   slot Momentum   (hp: momentum, use_nesterov)
-          adagrad   acc += g^2; var -= lr g / sqrt(acc)          slot Adagrad    (hp: initial_accumulator_value)
-          rmsprop   ms / mom as tf.train.RMSPropOptimizer        slots RMSProp, Momentum (hp: decay, momentum, epsilon)
-          ftrl      tf.train.FtrlOptimizer's SparseApplyFtrl (V2): acc' = acc + g^2;
-                    linear += g + 2 shrink var - (acc'^p - acc^p) / lr var;
-                    var = |linear| > l1 ? (sign(linear) l1 - linear) / (acc'^p / lr + 2 l2) : 0, p = -learning_rate_power
-                    slots Ftrl (accum), Ftrl_1 (linear)  (hp: learning_rate_power, initial_accumulator_value,
-                    l1_regularization_strength, l2_regularization_strength, l2_shrinkage_regularization_strength);
-                    a touched row with a summed gradient of 0 is still recomputed from `linear`
-          adam      tf.train.AdamOptimizer's _apply_sparse: m, v decay on EVERY row of the shard,
-                    the step moves every row (dense over the shard)  slots Adam, Adam_1 (hp: beta1, beta2, epsilon)
+        sparse-apply semantics (duplicates summed, then each touched row), by the
+        rule `kind` of optim/rules.py with `hp` under TF's names: sgd, momentum,
+        adagrad, rmsprop, ftrl (a touched row with a summed gradient of 0 is still
+        recomputed from `linear`) or adam (tf.train.AdamOptimizer's _apply_sparse:
+        m, v decay on EVERY row of the shard, the step moves every row).
 
         Row-local rules run one kernel over the step's touched rows
         (csrc/kernels/sparse_optim.hip); Adam runs the fused multi-tensor Adam
-        over the shard.  Slots are sharded like the table (`slot_view`)."""
-        if kind not in ("sgd", "momentum", "adagrad", "rmsprop", "adam", "ftrl"):
+        over the shard.  Slots carry the rule's TF names and are sharded like
+        the table (`slot_view`)."""
+        rule = RULES.get(kind)
+        if rule is None or not rule.sparse:
             raise ValueError(f"{self.name}: no sparse update rule '{kind}'")
-        if kind == "ftrl":
-            check_ftrl_hp(hp)
+        init = rule.slot_init(hp)           # checks the hyper-parameters as TF's constructor does
         if kind == self.opt_kind and hp == self.opt_hp:
             return
         self.opt_kind, self.opt_hp = kind, dict(hp)
-        self.slots, self._adam = {}, None
-        z = torch.zeros_like(self.local)
-        if kind == "momentum":
-            self.slots["Momentum"] = z
-        elif kind == "adagrad":
-            self.slots["Adagrad"] = z.fill_(float(hp.get("initial_accumulator_value", 0.1)))
-        elif kind == "rmsprop":
-            self.slots["RMSProp"] = torch.ones_like(self.local)
-            self.slots["Momentum"] = z
-        elif kind == "ftrl":
-            self.slots["Ftrl"] = torch.full_like(self.local, float(hp.get("initial_accumulator_value", 0.1)))
-            self.slots["Ftrl_1"] = z
-        elif kind == "adam":
+        self._adam = None
+        if rule.row_local:
+            self.slots = {n: torch.full_like(self.local, v0) for n, v0 in zip(rule.slots, init)}
+        else:
             from .. import optim
-            self._adam = optim.FusedAdam([self.local], 0.001, float(hp.get("beta1", 0.9)),
-                                         float(hp.get("beta2", 0.999)), float(hp.get("epsilon", 1e-8)))
-            self.slots["Adam"], self.slots["Adam_1"] = self._adam.m[0], self._adam.v[0]
+            self._adam = optim.fused(kind, [self.local], 0.001, **hp)
+            self.slots = dict(zip(rule.slots, (self._adam.m[0], self._adam.v[0])))
         self._empty = None if kind == "sgd" else torch.zeros(1, dtype=torch.int32, device=self.device)
         # [local rows + 1 dump row] accumulator of a step's summed gradients, zero between steps:
         # allocated by the first update through this path (_apply_local) -- the one-GPU
@@ -416,8 +399,8 @@ class ShardedEmbedding:
         nl = the dump row of padding), then clear them."""
         nl = self.local.shape[0]
         s, _ = torch.sort(i)
-        hp = self.opt_hp
-        if self.opt_kind == "adam":
+        rule = RULES[self.opt_kind]
+        if not rule.row_local:
             self._adam.set_lr(lr)
             self._adam.step([self._gacc[:nl]], skip=void)
         else:
@@ -425,18 +408,13 @@ class ShardedEmbedding:
             head[1:] = s[1:] != s[:-1]
             rows = torch.where(head & (s < nl), s, torch.full_like(s, -1))    # each touched row once
             gsum = self._gacc.index_select(0, s)
-            kind = {"momentum": 1, "adagrad": 4, "rmsprop": 5, "ftrl": 6}[self.opt_kind]
-            sa = self.slots.get("Adagrad", self.slots.get("RMSProp", self.slots.get("Ftrl", self.slots.get("Momentum"))))
-            sb = self.slots.get("Momentum") if self.opt_kind == "rmsprop" else self.slots.get("Ftrl_1")
-            mu = float(hp.get("momentum", 0.0))
-            args = (kind, float(lr), mu, bool(hp.get("use_nesterov", False)), float(hp.get("decay", 0.9)),
-                    float(hp.get("epsilon", 1e-10)))
-            fkw = ftrl_kwargs(hp) if kind == 6 else {}
+            sa, sb = (tuple(self.slots.values()) + (None, None))[:2]
             if self.local.is_cuda:
-                ops._C().sparse_rows_apply(self.local, sa, sb, rows, gsum, *args,
-                                           skip=None if void is None else void.reshape(-1)[:1].to(torch.int32), **fkw)
+                ops._C().sparse_rows_apply(self.local, sa, sb, rows, gsum, rule.kind, float(lr),
+                                           skip=None if void is None else void.reshape(-1)[:1].to(torch.int32),
+                                           **rule.native_kwargs(self.opt_hp))
             else:
-                _rows_apply_torch(self.local, sa, sb, rows, gsum, *args, skip=void, **fkw)
+                _rows_apply_torch(self.local, sa, sb, rows, gsum, rule, float(lr), self.opt_hp, skip=void)
         self._gacc.index_fill_(0, s, 0.0)
 
     # ------------------------------------------------------------------ bags
@@ -510,55 +488,17 @@ def lookup_shared(tables, ctx: LookupCtx):
     return list(rows.split(dims, 1)) if len(tables) > 1 else [rows]
 
 
-def check_ftrl_hp(hp: dict):
-    """tf.train.FtrlOptimizer's constructor checks on the sparse rule's hyper-parameters."""
-    if float(hp.get("initial_accumulator_value", 0.1)) < 0.0:
-        raise ValueError("initial_accumulator_value needs to be positive or zero")
-    if float(hp.get("learning_rate_power", -0.5)) > 0.0:
-        raise ValueError("learning_rate_power needs to be negative or zero")
-    for k in ("l1_regularization_strength", "l2_regularization_strength", "l2_shrinkage_regularization_strength"):
-        if float(hp.get(k, 0.0)) < 0.0:
-            raise ValueError(f"{k} needs to be positive or zero")
-
-
-def ftrl_kwargs(hp: dict) -> dict:
-    """The kernels' FTRL arguments from TF's hyper-parameter names."""
-    return {"lr_power": float(hp.get("learning_rate_power", -0.5)),
-            "l1": float(hp.get("l1_regularization_strength", 0.0)),
-            "l2": float(hp.get("l2_regularization_strength", 0.0)),
-            "l2_shrinkage": float(hp.get("l2_shrinkage_regularization_strength", 0.0))}
-
-
-def _rows_apply_torch(table, sa, sb, rows, g, kind, lr, mu, nesterov, rho, eps, skip=None, lr_power=-0.5, l1=0.0,
-                      l2=0.0, l2_shrinkage=0.0):
-    """CPU twin of csrc/kernels/sparse_optim.hip (same per-row math)."""
+def _rows_apply_torch(table, sa, sb, rows, g, rule, lr, hp, skip=None):
+    """CPU twin of csrc/kernels/sparse_optim.hip: the rule on the rows >= 0, nothing on a voided step."""
     if skip is not None and int(skip.reshape(-1)[0]) != 0:
         return
     keep = rows >= 0
-    r, gg = rows[keep], g[keep]
-    var = table[r]
-    if kind == 1:
-        acc = mu * sa[r] + gg
-        sa[r] = acc
-        table[r] = var - lr * (gg + mu * acc if nesterov else acc)
-    elif kind == 4:
-        acc = sa[r] + gg * gg
-        sa[r] = acc
-        table[r] = var - lr * gg * torch.rsqrt(acc)
-    elif kind == 5:
-        ms = rho * sa[r] + (1 - rho) * gg * gg
-        mom = mu * sb[r] + lr * gg * torch.rsqrt(ms + eps)
-        sa[r], sb[r] = ms, mom
-        table[r] = var - mom
-    elif kind == 6:
-        if sa is None or sb is None:
-            raise ValueError("FTRL needs its accum and linear slots")
-        from ..optim import ftrl_torch_
-        acc, lin = sa[r], sb[r]
-        ftrl_torch_(var, acc, lin, gg, lr, lr_power, l1, l2, l2_shrinkage)
-        table[r], sa[r], sb[r] = var, acc, lin
-    else:
-        table[r] = var - lr * gg
+    r = rows[keep]
+    state = [t[r] if t is not None else None for t in (table, sa, sb)]
+    rule.update_(*state, g[keep], lr, hp, fast_rsqrt=True)
+    for t, new in zip((table, sa, sb), state):
+        if t is not None:
+            t[r] = new
 
 
 def apply_sgd_shared(tables, ctx: LookupCtx, grads, lrs, grad_scale: float = 1.0):
