@@ -7,6 +7,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <tuple>
 
 extern "C" {
 int dtfk_bn_partial_rows(int M, int C);
@@ -46,6 +47,7 @@ hipError_t dtfk_conv_wflip_multi(const long long* tab, const int* tiles, int nti
 long long dtfk_conv_wgrad_plan(int N, int H, int W, int C, int K, int stride, int ks, int* splits_out, int* sps_out);
 hipError_t dtfk_conv_wgrad(const void* dy, const void* x, float* dw, float* ws, int N, int H, int W, int C, int K,
                            int stride, int ks, int kcrs, hipStream_t stream);
+long long dtfk_conv_wgrad_launch_plan(int N, int H, int W, int C, int K, int stride, int ks, int out[6]);
 long long dtfk_conv3x3_dx2_tiles(int N, int H, int W);
 int dtfk_conv3x3_dx2_supported(int N, int H, int W, int C, int K);
 hipError_t dtfk_conv3x3_dx2(const void* dy, const void* wt, void* dx, float* part, int N, int H, int W, int C, int K,
@@ -199,12 +201,17 @@ static void cl_bf16(const at::Tensor& t, const char* what) {
   if (!t.is_cuda() || t.scalar_type() != at::kBFloat16 || t.dim() != 4 || !t.is_contiguous(at::MemoryFormat::ChannelsLast))
     throw std::runtime_error(std::string(what) + ": channels_last bf16 4-D CUDA tensor expected");
 }
+// the kernels take stride 1 or 2; checked before any shape arithmetic divides by it
+static void stride_12(int64_t stride, const char* what) {
+  if (stride != 1 && stride != 2) throw std::runtime_error(std::string(what) + ": stride must be 1 or 2");
+}
 static int ksize(const at::Tensor& w) {
   if (w.dim() != 4 || w.size(2) != w.size(3) || (w.size(2) != 1 && w.size(2) != 3)) return 0;
   return (int)w.size(2);
 }
 
 bool conv3x3_supported(at::Tensor x, at::Tensor w, int64_t stride) {
+  if (stride != 1 && stride != 2) return false;
   const int ks = ksize(w);
   if (x.dim() != 4 || ks == 0 || w.size(1) != x.size(1)) return false;
   return dtfk_conv_supported((int)x.size(0), (int)x.size(2), (int)x.size(3), (int)x.size(1), (int)w.size(0),
@@ -224,6 +231,7 @@ int64_t conv3x3_tiles(int64_t N, int64_t H, int64_t W, int64_t stride) {
 void conv3x3_fwd(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Tensor> part, int64_t stride,
                  int64_t bn, bool accumulate, c10::optional<at::Tensor> bn_x, c10::optional<at::Tensor> bn_stats,
                  c10::optional<at::Tensor> bn_res) {
+  stride_12(stride, "conv_fwd");
   cl_bf16(x, "conv_fwd x");
   cl_bf16(w, "conv_fwd w");
   cl_bf16(y, "conv_fwd y");
@@ -256,6 +264,9 @@ void conv3x3_fwd(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Ten
     }
   } else if (bn_res.has_value()) {
     throw std::runtime_error("conv_fwd: bn_res needs bn_x");
+  } else if (pp != nullptr && accumulate) {
+    // the statistics epilogue sums the convolution alone, not the stored y + conv
+    throw std::runtime_error("conv_fwd: part with accumulate needs bn_x (statistics of y + conv are not computed)");
   }
   ck(dtfk_conv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), pp, N, H, W, C, K, (int)stride, (int)bn, ks,
                    accumulate ? 1 : 0, bx, bst, br, cs()),
@@ -335,6 +346,7 @@ void conv_wflip_multi(at::Tensor tab, at::Tensor tiles) {
 // dw (fp32 [K, C, ks, ks], channels_last or contiguous) += the weight gradient of
 // y = conv(x, w, stride) for y's gradient dy
 void conv3x3_wgrad(at::Tensor dy, at::Tensor x, at::Tensor dw, int64_t stride) {
+  stride_12(stride, "conv_wgrad");
   cl_bf16(dy, "conv_wgrad dy");
   cl_bf16(x, "conv_wgrad x");
   if (!dw.is_cuda() || dw.scalar_type() != at::kFloat || dw.dim() != 4 || dw.size(2) != dw.size(3) ||
@@ -357,6 +369,21 @@ void conv3x3_wgrad(at::Tensor dy, at::Tensor x, at::Tensor dw, int64_t stride) {
   ck(dtfk_conv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(), wsn > 0 ? ws.data_ptr<float>() : nullptr, N,
                      H, W, C, K, (int)stride, ks, kcrs, cs()),
      "conv_wgrad");
+}
+
+// The launch plan dtfk_conv_wgrad uses for this shape (read-only): (splits,
+// steps_per_split of 64 pixels, bm, bnw, xcd, G, workspace_floats) -- pixel
+// splits, the output-channel x filter-column tile, the XCD-aware workgroup
+// order, and the reduce's threads per output.
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> conv_wgrad_plan(
+    int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t stride, int64_t ks) {
+  stride_12(stride, "conv_wgrad_plan");
+  if (!dtfk_conv_supported((int)N, (int)H, (int)W, (int)C, (int)K, (int)stride, (int)ks))
+    throw std::runtime_error("conv_wgrad_plan: unsupported shape");
+  int p[6];
+  const long long wsn = dtfk_conv_wgrad_launch_plan((int)N, (int)H, (int)W, (int)C, (int)K, (int)stride, (int)ks, p);
+  return std::make_tuple((int64_t)p[0], (int64_t)p[1], (int64_t)p[2], (int64_t)p[3], (int64_t)p[4], (int64_t)p[5],
+                         (int64_t)wsn);
 }
 
 // BatchNorm backward when its output gradient arrived already ReLU-masked as g
@@ -392,6 +419,8 @@ void init_bn(pybind11::module& m) {
   m.def("bn_stat_partials", &bn_stat_partials);
   m.def("bn_bwd_parts", &bn_bwd_parts);
   m.def("conv3x3_wgrad", &conv3x3_wgrad);
+  m.def("conv_wgrad_plan", &conv_wgrad_plan, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("K"),
+        py::arg("stride"), py::arg("ks"));
   m.def("bn_fwd_parts", &bn_fwd_parts);
   m.def("conv3x3_supported", &conv3x3_supported);
   m.def("conv3x3_tiles", &conv3x3_tiles);

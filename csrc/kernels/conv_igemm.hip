@@ -1,4 +1,4 @@
-// Reached by: ops/conv.py ShadowConv2d (ResNet-50 convolutions); tests/test_conv_igemm_gpu.py, tests/test_conv_dx_stride2_gpu.py
+// Reached by: ops/conv.py ShadowConv2d (ResNet-50 convolutions); tests/test_conv_igemm_gpu.py, tests/test_conv_dx_stride2_gpu.py, tests/test_conv_igemm_edges_gpu.py (per element, against tests/conv_reference.py)
 // 3x3 (pad 1) and 1x1 (pad 0) convolutions, stride 1 or 2, on NHWC bf16
 // activations as implicit GEMMs on the gfx950 matrix cores, with an optional
 // BatchNorm statistics epilogue (ResNet-50, BASELINE.json configs[2]).  KS is
@@ -843,6 +843,8 @@ hipError_t dtfk_conv_fwd(const void* x, const void* w, void* y, float* part, int
   if (bnx != nullptr && (part == nullptr || bnst == nullptr || (bnres != nullptr) != (accum != 0)))
     return hipErrorInvalidValue;
   if (bnx == nullptr && bnres != nullptr) return hipErrorInvalidValue;
+  // EPI 1 sums the convolution alone: with accum they would not be the statistics of the stored y
+  if (bnx == nullptr && part != nullptr && accum) return hipErrorInvalidValue;
   const int epi = bnx != nullptr ? (bnres != nullptr ? 3 : 2) : (part != nullptr ? 1 : 0);
   auto bx = static_cast<const uint16_t*>(bnx);
   auto br = static_cast<const uint16_t*>(bnres);
@@ -1018,6 +1020,31 @@ long long dtfk_conv3x3_wgrad_plan(int N, int H, int W, int C, int K, int stride,
   return dtfk_conv_wgrad_plan(N, H, W, C, K, stride, 3, splits_out, sps_out);
 }
 
+// The whole launch plan of the weight gradient, for dtfk_conv_wgrad and for callers
+// that want to see it: out = {splits, steps_per_split, bm, bnw, xcd, G}; returns
+// the workspace floats.  bm x bnw: the tile (output channels x filter columns),
+// xcd: the XCD-aware workgroup order, G: reduce threads per output.
+long long dtfk_conv_wgrad_launch_plan(int N, int H, int W, int C, int K, int stride, int ks, int out[6]) {
+  const int NC = ks * ks * C;
+  const int bm = K % 128 == 0 ? 128 : 64;
+  const int bnw = wgrad_bnw(NC);
+  int splits = 1, sps = 1;
+  const long long wsn = dtfk_conv_wgrad_plan(N, H, W, C, K, stride, ks, &splits, &sps);
+  const long long slab = wsn > 0 ? wsn / splits : 0;
+  const int tiles_x = K / bm, tiles_y = (NC + bnw - 1) / bnw;
+  const int xcd = (wgrad_xcd((long long)tiles_x * tiles_y) && splits >= 8 && splits % 8 == 0) ? 1 : 0;
+  // reduce threads per output: up to 16, ~128K threads in all
+  int G = 1;
+  while (G < 16 && 2 * G <= splits && (slab / 4) * G < 131072) G *= 2;
+  out[0] = splits;
+  out[1] = sps;
+  out[2] = bm;
+  out[3] = bnw;
+  out[4] = xcd;
+  out[5] = G;
+  return wsn;
+}
+
 // dW (fp32 [K][ks][ks][C] channels_last or [K][C][ks][ks] with kcrs, accumulated
 // into) of y = conv(x, w, stride); dy is y's gradient; ws: dtfk_conv_wgrad_plan's
 // workspace (may be null when it is 0)
@@ -1029,20 +1056,15 @@ hipError_t dtfk_conv_wgrad(const void* dy, const void* x, float* dw, float* ws, 
   const long long P = (long long)N * Ho * Wo;
   if (P * K * 2 >= 0x7ffffff0LL) return hipErrorInvalidValue;
   const int NC = ks * ks * C;
-  const int bm = K % 128 == 0 ? 128 : 64;
-  const int bnw = wgrad_bnw(NC);
-  int splits = 1, sps = 1;
-  const long long wsn = dtfk_conv_wgrad_plan(N, H, W, C, K, stride, ks, &splits, &sps);
+  int plan[6];
+  const long long wsn = dtfk_conv_wgrad_launch_plan(N, H, W, C, K, stride, ks, plan);
+  const int splits = plan[0], sps = plan[1], bm = plan[2], bnw = plan[3], xcd = plan[4], G = plan[5];
   if (wsn > 0 && ws == nullptr) return hipErrorInvalidValue;
   float* wsp = wsn > 0 ? ws : nullptr;
   const long long slab = wsn > 0 ? wsn / splits : 0;
   const int tiles_x = K / bm, tiles_y = (NC + bnw - 1) / bnw;
   const dim3 grid((unsigned)(tiles_x * tiles_y * splits));
-  const int xcd = (wgrad_xcd((long long)tiles_x * tiles_y) && splits >= 8 && splits % 8 == 0) ? 1 : 0;
   const long long xbytes = (long long)N * H * W * C * 2;
-  // reduce threads per output: up to 16, ~128K threads in all
-  int G = 1;
-  while (G < 16 && 2 * G <= splits && (slab / 4) * G < 131072) G *= 2;
   auto d = static_cast<const uint16_t*>(dy);
   auto xs = static_cast<const uint16_t*>(x);
   // operand sets in flight (DTF_CONV_WGRAD_DEPTH: 2 or 3; 3 where it keeps the occupancy)
