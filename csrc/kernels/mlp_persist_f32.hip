@@ -27,17 +27,27 @@
 //          the B operand straight from the accumulator layout).
 //      E2  partial logits go to the workgroup of the same slice in every other
 //          block; logits = b2 + sum_j (block order) -> identical in all 28.
-//          softmax / cross-entropy / argmax, dz3, da2 = W2 dz3 (4 MFMAs),
-//          dz2 = da2 * act' -> LDS.
+//          The head's chain is only what dz2 needs: logits, m, ex, ssum, inv,
+//          dz3, da2 = W2 dz3 (4 MFMAs), dz2 = da2 * act' -> LDS with the dz3 /
+//          a2 rows, then the FIRST head flag.  Behind it: the row's loss / hit
+//          (zy, argmax; the label's probability only for the naive loss) in
+//          workgroup 0 alone -- nobody else reads them --, the tile's dW2 / db2
+//          partial (8 MFMAs), then the SECOND head flag.
 //      P2  dW1 tiles = x^T dz2 over the batch (28 MFMAs per tile, x^T bytes by
 //          transposing LDS reads of the same row-major image the forward
 //          reads: ds_read_b64_tr_b8), W1 -= lr/(255 B) dW1 in registers;
-//          wave 7 also: dW2 (28 MFMAs), db1, db2, metrics, update of the LDS
+//          wave 7 also, once the seven second flags are up: the fold of the
+//          tiles' dW2 / db2 partials, db1, metrics, update of the LDS
 //          copies of W2[block j], b1[block j], b2 -- identical in every
 //          workgroup that holds them (same inputs, same order).
 //      P2 runs without a workgroup barrier: each 32-row batch chunk of the
 //          weight gradient starts as soon as the heads of its batch tiles have
-//          set their LDS flags; wave 7 signals the next step's stage with a flag.
+//          set their first LDS flags (the partial that only wave 7's fold consumes
+//          is not in front of them); wave 7 signals the next step's stage with a
+//          flag.  The head was the step's longest compute segment and two heads
+//          serialise on a SIMD: 311 -> 192 instructions from the E2 gather to the
+//          last head MFMA in 27 workgroups, 280 -> 164 to the last dz2 plane
+//          store (profiles/mlp_persist_f32_head_ab.json).
 //      Operand preparation (one-GPU split engine, PREP in compute()): the pixel
 //          bytes become bf16 MFMA operands away from the MFMAs that use them --
 //          the step's x^T operands of P2 in the E1 window (wave 7: behind its
@@ -49,10 +59,14 @@
 //          last step prepares nothing).  P0 is split8 + MFMAs, and only the dz2
 //          piece reads sit between a head flag and a chunk's MFMAs.  Same
 //          operands, same order: same bits.
-//      Workgroup 0's metrics (same engine, MET_FAST in compute()): its wave 7
-//          reduces the per-row loss / accuracy in front of barrier A, which made
-//          workgroup 0 the last to publish at every E1; the same sums by VALU
-//          lane permutes, and the ring slot by a 32-bit modulo.
+//      Workgroup 0's metrics: its head waves write the per-row loss / hit behind
+//          their first flag and in front of their second one, and its wave 7
+//          reduces them in front of barrier A (MET_FAST in compute(), same
+//          engine: the sums by VALU lane permutes, the ring slot by a 32-bit
+//          modulo).  Workgroup 0's wave 7 still reaches barrier A after the
+//          others'; handing the rows of tiles 4..6 to waves 0..2, and a flag of
+//          their own for the rows behind the partial, were built bit-equal,
+//          measured and taken out (figures: profiles/mlp_persist_f32_head_ab.json).
 //    One LDS barrier and two inter-workgroup edges per step; the data of
 //    every edge is double-buffered by step parity and tagged with the global
 //    exchange sequence number, so buffers are never reset between launches.
@@ -182,7 +196,7 @@ constexpr int XF_CHUNKS = BROWS * 13;                  // gradient's K = 128 bat
 constexpr int L_LAB = L_XF + XTS * XF_ROW;             // [128] labels
 constexpr int PS = XTS + 8;                            // split mode: bf16 plane row stride (elements)
 constexpr int L_DZP = L_LAB + 128;                     // split mode: [3 pieces][16 hidden][PS] dz2 bf16
-constexpr int L_HFLAG = L_DZP + 3 * 16 * PS * 2;       // [8] head-done flags (step + 1) of waves 0..6
+constexpr int L_HFLAG = L_DZP + 3 * 16 * PS * 2;       // [16] flags (step + 1): 0..6 head of batch tile v, 7 stage, 8..14 its partials
 constexpr int L_DW2P = L_HFLAG + 64;                   // [7 batch tiles][64 lanes] f32x4 dW2 partials
 constexpr int L_RLOSS = L_DW2P + NBT * 64 * 16;        // [2][128] per-row loss / correct of the step
 constexpr int LDS_COMPUTE = L_RLOSS + 2 * 128 * 4;
@@ -249,7 +263,10 @@ struct Args {
                             // sub-phase stamps (slots 13-15, wave 0), bit 2 = wave 7 too prepares the next
                             // step's operands on the late path, after P2 (same bits as its early path:
                             // tests/test_mlp_persist_operand_prep_gpu.py), bit 3 = step-boundary stamps
-                            // of every wave (PHB below; needs phase_ts)
+                            // of every wave (PHB below; needs phase_ts), bit 4 = the weight-gradient
+                            // chunks wait for the heads' second flag, behind the dW2 / db2 partial and
+                            // workgroup 0's loss / hit rows (one flag's order, same bits:
+                            // tests/test_mlp_persist_head_gpu.py)
 };
 
 // resident per-run stamp (s_memrealtime, 100 MHz) -- profiling only: 0 copier 0
@@ -275,7 +292,7 @@ struct Args {
   if ((dbg & 2) == 0) { PH(ph); }
 // DTF_PERSIST_DBG bit 3: step-boundary stamps of every wave, lane 0, in the 16
 // slots of the unused workgroup row 32 + c (the rows of c keep wave 0's stamps):
-// w = wave w arrives at barrier A, 8 + w = head wave w done (flag set), 15 = wave
+// w = wave w arrives at barrier A, 8 + w = head wave w done (first flag set), 15 = wave
 // 7's W2 / b1 / b2 updates stored.  Wave 7's slot 15 of row c is then its last
 // chunk's MFMAs issued (not the stage landing)
 #define PHB(slot)                                                                                \
@@ -964,7 +981,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
     b2s[tid - 272] = pv;
   } else if (tid == 288) {
     *abort_flag = 0;
-  } else if (tid >= 296 && tid < 304) {
+  } else if (tid >= 296 && tid < 312) {
     reinterpret_cast<int*>(smem + L_HFLAG)[tid - 296] = 0;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // parameter loads + the first stage landed
@@ -1169,12 +1186,18 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
     const bool more = !RES && st + 1 < a.nsteps;   // RES: the next run's record is staged at its top
     // everyone's reads of this step's stage retired at barrier A: wave 7 (idle
     // until P2) stages the next step while the others run the edges and the head
-    int* hflag = reinterpret_cast<int*>(smem + L_HFLAG);   // [0..6] head of batch tile v done; [7] stage landed
-    auto heads_done = [&]() -> unsigned {   // bit v: head of batch tile v finished this step
-      const bool ok = lane < NBT && __hip_atomic_load(hflag + (lane < NBT ? lane : 0), __ATOMIC_RELAXED,
+    // [0..6] head of batch tile v: dz2 pieces, dz3 / a2 rows in LDS; [7] stage landed;
+    // [8..14] head of batch tile v: dW2 / db2 partial (workgroup 0: loss / hit rows) in LDS
+    int* hflag = reinterpret_cast<int*>(smem + L_HFLAG);
+    auto flags_up = [&](int f0) -> unsigned {   // bit v: flag f0 + v set this step
+      const bool ok = lane < NBT && __hip_atomic_load(hflag + f0 + (lane < NBT ? lane : 0), __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_WORKGROUP) >= st + 1;
       return (unsigned)__ballot(ok) & ((1u << NBT) - 1u);
     };
+    // a chunk waits for the first flag of its batch tiles (DTF_PERSIST_DBG bit 4: for
+    // the second, the order in which one flag covered the partials as well)
+    const int chunk_flag = (dbg & 16) != 0 ? 8 : 0;
+    auto heads_done = [&]() -> unsigned { return flags_up(chunk_flag); };
     if (w == 7 && more && !(dbg & 1)) {
       stage_x(st + 1, 0, 1);
       // idle until the first head is done anyway: wait for the DMA here and tell the
@@ -1259,7 +1282,9 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       ok = gather_gran<NJ>(r2, [&](int k) { return k * GSLOT; }, jq[0], g < 3, tag, pl, lp, lane, a) && ok;
       if (w == 0) { PH(7); }
       if (!ok && lane == 0) *abort_flag = 1;
-      // logits, softmax cross-entropy, accuracy -- identical in every workgroup
+      // logits and softmax -- identical in every workgroup.  Only what dz3 needs
+      // (m, ssum, the label) sits on the chain to the dz2 stores; the row's loss and
+      // hit come after the first head flag, in workgroup 0 alone
       float lg[4], ex[4];
       float m = -3.0e38f;
 #pragma unroll
@@ -1274,30 +1299,25 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       m = fmaxf(m, xor16(m));
       m = fmaxf(m, xor32(m));
       const int y = lab < NCLS ? lab : 0;
-      float ssum = 0.f, zy = 0.f, am = 1e9f;
+      float ssum = 0.f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int cl = 4 * g + i;
-        ex[i] = cl < NCLS ? __expf(lg[i] - m) : 0.f;
+        ex[i] = 4 * g + i < NCLS ? __expf(lg[i] - m) : 0.f;
         ssum += ex[i];
-        zy += (cl == y) ? lg[i] : 0.f;
-        if (cl < NCLS && lg[i] == m) am = fminf(am, (float)cl);
       }
       ssum += xor16(ssum); ssum += xor32(ssum);
-      zy += xor16(zy); zy += xor32(zy);
-      am = fminf(am, xor16(am)); am = fminf(am, xor32(am));
       const float inv = __builtin_amdgcn_rcpf(ssum);
       if (w == 0) { PHX(13); }
-      float dz3[4], py = 0.f;
+      float pr[4], dz3[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int cl = 4 * g + i;
-        const float p = ex[i] * inv;
-        py += (cl == y) ? p : 0.f;
-        dz3[i] = (bv && cl < NCLS) ? p - (cl == y ? 1.f : 0.f) : 0.f;   // unscaled: 1/B at the update
+        pr[i] = ex[i] * inv;
+        // the rounded product, as when py summed it in front of dz3: not contracted
+        // into an fma with the subtraction below (other bits in dz3)
+        asm("" : "+v"(pr[i]));
+        dz3[i] = (bv && cl < NCLS) ? pr[i] - (cl == y ? 1.f : 0.f) : 0.f;   // unscaled: 1/B at the update
       }
-      py += xor16(py); py += xor32(py);
-      const float loss = a.naive ? -__logf(py) : (m + __logf(ssum) - zy);
       // da2^T = W2 . dz3^T (A = W2, lane: hidden r), dz2 = da2 * act'(a2)
       f32x4 da = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1319,11 +1339,45 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         dz3T[(4 * g + i) * LS + bw] = dz3[i];
       }
       if (w == 0) { PHX(15); }
-      // per-row loss / hit, summed by wave 7 (no row reductions on the head's path)
-      if (g == 0) {
-        float* rl = reinterpret_cast<float*>(smem + L_RLOSS);
-        rl[bw] = bv ? loss : 0.f;
-        rl[128 + bw] = (bv && (int)am == y) ? 1.f : 0.f;
+      // first head flag: the tile's dz2 pieces and its dz3 / a2 rows are in LDS --
+      // all a weight-gradient chunk waits for
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      if (lane == 0) __hip_atomic_store(hflag + w, st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (w == 0) { PH(9); }
+      PHB(8 + w);
+      // the row's loss and hit, read by workgroup 0's wave 7 and by nobody else
+      // (workgroup-uniform branch): zy and the argmax over the 4 lane groups, py =
+      // the label's ex * inv product for the naive loss only -- the operands and the
+      // order they had in front of dz3.  The label is laundered so its class masks
+      // are compared again here and not carried in SGPRs across the MFMAs (the
+      // kernel sits at its SGPR limit).
+      if (c == 0) {
+        int ym = y;
+        asm volatile("" : "+v"(ym));
+        float zy = 0.f, am = 1e9f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int cl = 4 * g + i;
+          zy += (cl == ym) ? lg[i] : 0.f;
+          if (cl < NCLS && lg[i] == m) am = fminf(am, (float)cl);
+        }
+        zy += xor16(zy); zy += xor32(zy);
+        am = fminf(am, xor16(am)); am = fminf(am, xor32(am));
+        float loss;
+        if (a.naive) {
+          float py = 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) py += (4 * g + i == ym) ? pr[i] : 0.f;
+          py += xor16(py); py += xor32(py);
+          loss = -__logf(py);
+        } else {
+          loss = m + __logf(ssum) - zy;
+        }
+        if (g == 0) {
+          float* rl = reinterpret_cast<float*>(smem + L_RLOSS);
+          rl[bw] = bv ? loss : 0.f;
+          rl[128 + bw] = (bv && (int)am == ym) ? 1.f : 0.f;
+        }
       }
       // this tile's dW2 = a2^T dz3 and db2 = 1^T dz3 partials over its 16 rows (two
       // independent f32 MFMA chains; k = batch 4g + e, from the rows this wave just
@@ -1343,14 +1397,10 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         reinterpret_cast<f32x4*>(smem + L_DW2P)[w * 64 + lane] = dp;
         if (g == 0) rdb2[w * 16 + r] = p2[0];   // D[0][class r]
       }
-      // head of batch tile w done (dz2 / dz3 / a2 rows and the row metrics are in LDS,
-      // its reads of W2 / b1 / b2 are over)
+      // second head flag: the tile's dW2 / db2 partial (workgroup 0: its loss / hit
+      // rows too) is in LDS -- what wave 7's fold and metric reduction wait for
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      if (lane == 0)
-        __hip_atomic_store(reinterpret_cast<int*>(smem + L_HFLAG) + w, st + 1, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (w == 0) { PH(9); }
-      PHB(8 + w);
+      if (lane == 0) __hip_atomic_store(hflag + 8 + w, st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     // ---------------- P2 without a workgroup barrier: a wave multiplies the weight-
     // gradient chunk of batch rows 32cc..32cc+31 (one batch tile without SPLIT) as
@@ -1435,9 +1485,10 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
 #pragma unroll
       for (int k = 0; k < NTW; ++k) G[k] = G[k] + G1[k];
     }
-    // every head is done here.  Wave 7 sums the 7 head waves' dW2 / db2 partials
-    // and the per-row metrics in fixed order (all loads in flight at once); one
-    // GPU: the W2 / b1 / b2 updates too (their readers, this step's heads, are done;
+    // every head has set its first flag here.  Wave 7 waits for the seven second
+    // flags, then sums the 7 head waves' dW2 / db2 partials and the per-row metrics
+    // in fixed order (all loads in flight at once); one GPU: the W2 / b1 / b2
+    // updates too (their readers, this step's heads, took them in the E1 window;
     // the next step's read them after barrier A)
     f32x4 D = {0.f, 0.f, 0.f, 0.f};      // wave 7: dW2[16j+4g+i][class r] (x B)
     float gb = 0.f;                      // wave 7: db1 (lanes < 16) / db2 (lanes 16..25) (x B)
@@ -1445,6 +1496,9 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
       if constexpr (INS) {
         if ((dbg & 8) != 0) { PH7(15); }
       }
+      // its own chunks are multiplied: now the seven second flags
+      while (flags_up(8) != (1u << NBT) - 1u) __builtin_amdgcn_s_sleep(0);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
       // lanes 16..25: db2 column lane - 16 (lanes < 16 take db1 from the ones tile)
       const float* gsrc = rdb2 + (lane >= 16 && lane < 16 + NCLS ? lane - 16 : 0);
       const f32x4* dw2p = reinterpret_cast<const f32x4*>(smem + L_DW2P);

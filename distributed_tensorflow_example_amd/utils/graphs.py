@@ -18,6 +18,7 @@ next replay (copy it to keep it).
 """
 from __future__ import annotations
 
+import gc
 from collections import OrderedDict
 from typing import Callable, List, Sequence
 
@@ -81,8 +82,18 @@ class GraphedStep:
         from .. import ops
         g = torch.cuda.CUDAGraph()
         ops.bump_capture_epoch()          # no eager-cached sort / bag plan inside the graph
-        with torch.cuda.graph(g):
-            out = self.step_fn(*static_in)
+        # no cyclic collection inside the capture: a finalizer of older garbage (a
+        # runner's pinned buffers, another graph) may call into HIP, which a
+        # capturing stream answers with an error thrown from a destructor -- an abort
+        gc_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                out = self.step_fn(*static_in)
+        finally:
+            if gc_on:
+                gc.enable()
         ops.bump_capture_epoch()          # nor a captured one in later eager calls
         with torch.no_grad():
             for t, s in zip(self.state(), saved):

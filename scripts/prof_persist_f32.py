@@ -3,8 +3,10 @@ from in-kernel s_memrealtime stamps (100 MHz).
 
 Stamps per step (workgroup c, wave 0, lane 0): 0 step start, 1 forward MFMAs
 done, 2 after LDS barrier A, 3 E1 published, 4 E1 flags matched, 5 z summed,
-6 E2 published, 7 E2 flags matched, 8 logits summed, 9 head done, 10 first
-weight-gradient chunk's heads seen done (there is no barrier B: the chunk's dz2
+6 E2 published, 7 E2 flags matched, 8 logits summed, 9 head done (its first
+flag: dz2 pieces, dz3 / a2 rows in LDS; the dW2 / db2 partial and workgroup 0's
+loss / hit rows follow, then the second flag that wave 7's fold waits for), 10
+first weight-gradient chunk's heads seen done (there is no barrier B: the chunk's dz2
 piece reads and MFMAs follow), 11 weight-gradient MFMAs done (and, on the late
 path, the next step's operands read and converted), 12 update done.
 Wave 7, lane 0: 13 last head tile folded, 14 step start, 15 next step's stage
@@ -14,9 +16,9 @@ forward operands: wave 7 behind its own stage DMA (early path), the head waves
 after P2, inside wgrad_mfma -- they have no early path (DTF_PERSIST_DBG=4 puts
 wave 7 on the late path too).
 DTF_PERSIST_DBG=8 adds the step-boundary stamps of every wave (step_boundary
-below: arrivals at barrier A, head-done times, wave 7's tail, workgroup 0's
-wave 7 against the others'); slot 15 is then wave 7's last chunk, not the stage
-landing.
+below: arrivals at barrier A, head-done times, wave 7's tail, every wave of
+workgroup 0 against the same wave of the others); slot 15 is then wave 7's last
+chunk, not the stage landing.
 Prints the median / p90 of every segment over steps 1..63 and all compute
 workgroups, plus per-step time and launch-level timing.
 """
@@ -70,6 +72,20 @@ def step_boundary(raw, nwg):
     o["workgroup0_wave7_behind_median_of_others_us_median"] = {
         "updates_stored": med(upd[:, 0] - np.median(upd[:, 1:], axis=1)),
         "next_barrier_A_arrival": med(nxt[:, 0] - np.median(nxt[:, 1:], axis=1))}
+    # workgroup 0's head waves carry the per-row loss / hit the other 27 skip: every
+    # wave of workgroup 0 against the same wave's median over the others, per step,
+    # on the device clock (not from each workgroup's own step start); head-done is
+    # the first head flag, the one the chunks wait for
+    hda, arra = b1[s, :, 8:15], b1[s + 1, :, 0:8]
+    behind = lambda x: med(x[:, 0] - np.median(x[:, 1:], axis=1))
+    o["workgroup0_behind_median_of_others_us_median_by_wave"] = {
+        "head_done": [behind(hda[:, :, w]) for w in range(7)],
+        "next_barrier_A_arrival": [behind(arra[:, :, w]) for w in range(8)]}
+    o["workgroup0_wave7_behind_median_of_others_us_median"].update(
+        {"last_chunk_issued": behind(w7["last_chunk_issued"]), "fold_done": behind(w7["fold_done"])})
+    la = arra.max(2)
+    o["workgroup0_last_arrival_behind_median_of_others_us_median_p90"] = [
+        med(la[:, 0] - np.median(la[:, 1:], axis=1)), p90(la[:, 0] - np.median(la[:, 1:], axis=1))]
     return o
 
 
