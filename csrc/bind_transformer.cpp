@@ -58,13 +58,25 @@ void req(const at::Tensor& t, at::ScalarType dt, const char* n) {
 void* optp(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
 float* optf(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr<float>() : nullptr; }
 int rows_of(const at::Tensor& t, int H) { return (int)(t.numel() / H); }
+// size and range refusals, raised before any launch
+void need(bool ok, const char* what) {
+  if (!ok) throw std::runtime_error(what);
+}
+void need_p(double p, const char* op) {
+  need(p >= 0.0 && p < 1.0, (std::string(op) + ": dropout p must be in [0, 1)").c_str());
+}
+// the last dimension as the row width: at least 1, so that rows_of can divide by it
+int width_of(const at::Tensor& t, const char* op) {
+  need(t.dim() >= 1 && t.size(-1) > 0, (std::string(op) + ": the last dimension is empty").c_str());
+  return (int)t.size(-1);
+}
 }  // namespace
 
 // y = LN(dropout(x + bias) + res) ; x, res, y, s bf16 [N, H]; bias/gamma/beta fp32 [H]
 void bdrln_fwd(at::Tensor x, at::Tensor bias, c10::optional<at::Tensor> res, at::Tensor gamma, at::Tensor beta,
                at::Tensor y, c10::optional<at::Tensor> s, at::Tensor mean, at::Tensor rstd, double eps, double p,
                int64_t seed) {
-  const int H = (int)x.size(-1);
+  const int H = width_of(x, "bdrln_fwd");
   req(x, at::kBFloat16, "x"); req(y, at::kBFloat16, "y"); req(bias, at::kFloat, "bias");
   req(gamma, at::kFloat, "gamma"); req(beta, at::kFloat, "beta"); req(mean, at::kFloat, "mean");
   req(rstd, at::kFloat, "rstd");
@@ -72,6 +84,10 @@ void bdrln_fwd(at::Tensor x, at::Tensor bias, c10::optional<at::Tensor> res, at:
   if (s.has_value()) req(*s, at::kBFloat16, "s");
   const int N = rows_of(x, H);
   if (mean.numel() < N || rstd.numel() < N || y.numel() != x.numel()) throw std::runtime_error("bdrln_fwd shapes");
+  need(bias.numel() >= H && gamma.numel() >= H && beta.numel() >= H, "bdrln_fwd: bias / gamma / beta need H elements");
+  need(!res.has_value() || res->numel() == x.numel(), "bdrln_fwd: res size");
+  need(!s.has_value() || s->numel() == x.numel(), "bdrln_fwd: s size");
+  need_p(p, "bdrln_fwd");
   ck(dtfk_bdrln_fwd(x.data_ptr(), bias.data_ptr<float>(), optp(res), gamma.data_ptr<float>(), beta.data_ptr<float>(),
                     y.data_ptr(), optp(s), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H, (float)eps,
                     (float)p, (unsigned long long)seed, cs()),
@@ -80,10 +96,16 @@ void bdrln_fwd(at::Tensor x, at::Tensor bias, c10::optional<at::Tensor> res, at:
 
 void ln_fwd_f32in(at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor y, c10::optional<at::Tensor> s,
                   at::Tensor mean, at::Tensor rstd, double eps, double p, int64_t seed) {
-  const int H = (int)x.size(-1);
+  const int H = width_of(x, "ln_fwd_f32in");
   req(x, at::kFloat, "x"); req(y, at::kBFloat16, "y");
+  req(gamma, at::kFloat, "gamma"); req(beta, at::kFloat, "beta"); req(mean, at::kFloat, "mean");
+  req(rstd, at::kFloat, "rstd");
   if (s.has_value()) req(*s, at::kBFloat16, "s");
   const int N = rows_of(x, H);
+  need(y.numel() == x.numel() && (!s.has_value() || s->numel() == x.numel()), "ln_fwd_f32in: y / s size");
+  need(gamma.numel() >= H && beta.numel() >= H, "ln_fwd_f32in: gamma / beta need H elements");
+  need(mean.numel() >= N && rstd.numel() >= N, "ln_fwd_f32in: mean / rstd need N elements");
+  need_p(p, "ln_fwd_f32in");
   ck(dtfk_ln_fwd_f32in(x.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), y.data_ptr(), optp(s),
                        mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H, (float)eps, (float)p,
                        (unsigned long long)seed, cs()),
@@ -103,6 +125,8 @@ void emb_ln_fwd(at::Tensor word, at::Tensor ids, at::Tensor typ, at::Tensor tt, 
   if (tt.numel() != N || y.numel() != N * H || s.numel() != N * H || mean.numel() < N || rstd.numel() < N ||
       typ.size(-1) != H || pos.size(-1) != H || pos.size(0) < S || S < 1 || N % S)
     throw std::runtime_error("emb_ln_fwd shapes");
+  need(N >= 1 && H >= 1 && gamma.numel() >= H && beta.numel() >= H, "emb_ln_fwd: gamma / beta need H elements");
+  need_p(p, "emb_ln_fwd");
   ck(dtfk_emb_ln_fwd(word.data_ptr<float>(), ids.data_ptr<int64_t>(), typ.data_ptr<float>(), tt.data_ptr<int64_t>(),
                      pos.data_ptr<float>(), (int)S, gamma.data_ptr<float>(), beta.data_ptr<float>(), y.data_ptr(),
                      s.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), (int)N, H, (float)eps, (float)p,
@@ -133,13 +157,24 @@ void ln_bwd(at::Tensor dy, at::Tensor s, at::Tensor mean, at::Tensor rstd, at::T
             c10::optional<at::Tensor> dxb, at::Tensor part, c10::optional<at::Tensor> dgamma,
             c10::optional<at::Tensor> dbeta, c10::optional<at::Tensor> dbias, double p, int64_t seed,
             bool accumulate) {
-  const int H = (int)dy.size(-1);
+  const int H = width_of(dy, "ln_bwd");
   req(dy, at::kBFloat16, "dy"); req(s, at::kBFloat16, "s"); req(ds, at::kBFloat16, "ds");
-  req(part, at::kFloat, "part");
+  req(part, at::kFloat, "part"); req(mean, at::kFloat, "mean"); req(rstd, at::kFloat, "rstd");
+  req(gamma, at::kFloat, "gamma");
   if (dxb.has_value()) req(*dxb, at::kBFloat16, "dxb");
   const int N = rows_of(dy, H);
   const int grid = (int)(part.numel() / (3LL * H));
   if (grid < 1) throw std::runtime_error("ln_bwd: partial buffer too small (needs 3*grid*H floats)");
+  need(s.numel() == dy.numel() && ds.numel() == dy.numel() && (!dxb.has_value() || dxb->numel() == dy.numel()),
+       "ln_bwd: s / ds / dxb size");
+  need(mean.numel() >= N && rstd.numel() >= N, "ln_bwd: mean / rstd need N elements");
+  need(gamma.numel() >= H, "ln_bwd: gamma needs H elements");
+  need_p(p, "ln_bwd");
+  for (const auto* t : {&dgamma, &dbeta, &dbias})
+    if (t->has_value()) {
+      req(**t, at::kFloat, "param grad");
+      need((*t)->numel() >= H, "ln_bwd: gradient output too small");
+    }
   float* pg = part.data_ptr<float>();
   float* pb = pg + (size_t)grid * H;
   float* px = pb + (size_t)grid * H;
@@ -167,7 +202,7 @@ void ln_bwd(at::Tensor dy, at::Tensor s, at::Tensor mean, at::Tensor rstd, at::T
 // bias gradient of a bf16 [N, H] matrix: out (+)= column sums (part: P*H floats)
 void colsum_bf16(at::Tensor x, at::Tensor part, at::Tensor out, bool accumulate) {
   req(x, at::kBFloat16, "x"); req(part, at::kFloat, "part"); req(out, at::kFloat, "out");
-  const int H = (int)x.size(-1);
+  const int H = width_of(x, "colsum_bf16");
   const int N = rows_of(x, H);
   const int P = (int)(part.numel() / H);
   if (P < 1 || out.numel() < H) throw std::runtime_error("colsum_bf16 shapes");
@@ -187,8 +222,9 @@ void slab_sum(at::Tensor slabs, at::Tensor out, bool accumulate) {
 
 void bias_gelu_fwd(at::Tensor x, at::Tensor bias, at::Tensor y) {
   req(x, at::kBFloat16, "x"); req(y, at::kBFloat16, "y"); req(bias, at::kFloat, "bias");
-  const int H = (int)x.size(-1);
+  const int H = width_of(x, "bias_gelu_fwd");
   if (H % 4) throw std::runtime_error("bias_gelu: H % 4 != 0");
+  need(bias.numel() >= H && y.numel() == x.numel(), "bias_gelu_fwd: bias needs H elements, y the size of x");
   ck(dtfk_bias_gelu_fwd(x.data_ptr(), bias.data_ptr<float>(), y.data_ptr(), x.numel(), H, cs()), "bias_gelu_fwd");
 }
 
@@ -196,10 +232,12 @@ void bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias, at::Tensor dx, 
                    bool accumulate) {
   req(dy, at::kBFloat16, "dy"); req(x, at::kBFloat16, "x"); req(dx, at::kBFloat16, "dx");
   req(part, at::kFloat, "part"); req(dbias, at::kFloat, "dbias");
-  const int H = (int)x.size(-1);
+  const int H = width_of(x, "bias_gelu_bwd");
   const int N = rows_of(x, H);
   const int slices = (int)(part.numel() / H);
   if (slices < 1 || H % 4) throw std::runtime_error("bias_gelu_bwd shapes");
+  need(bias.numel() >= H && dbias.numel() >= H && dy.numel() == x.numel() && dx.numel() == x.numel(),
+       "bias_gelu_bwd: bias / dbias need H elements, dy / dx the size of x");
   ck(dtfk_bias_gelu_bwd(dy.data_ptr(), x.data_ptr(), bias.data_ptr<float>(), dx.data_ptr(), part.data_ptr<float>(), N,
                         H, slices, cs()),
      "bias_gelu_bwd");
@@ -213,8 +251,13 @@ void softmax_fwd(at::Tensor S, c10::optional<at::Tensor> mask, at::Tensor P, c10
   req(S, at::kBFloat16, "S"); req(P, at::kBFloat16, "P");
   if (Pd.has_value()) req(*Pd, at::kBFloat16, "Pd");
   if (mask.has_value()) req(*mask, at::kFloat, "mask");
-  const int Sk = (int)S.size(-1);
+  const int Sk = width_of(S, "softmax_fwd");
   const int rows = (int)(S.numel() / Sk);
+  need(rows_per_batch >= 1, "softmax_fwd: rows_per_batch must be at least 1");
+  need(P.numel() == S.numel() && (!Pd.has_value() || Pd->numel() == S.numel()), "softmax_fwd: P / Pd size");
+  need(!mask.has_value() || mask->numel() >= ((int64_t)rows + rows_per_batch - 1) / rows_per_batch * Sk,
+       "softmax_fwd: mask needs ceil(rows / rows_per_batch) * Sk elements");
+  need_p(p, "softmax_fwd");
   ck(dtfk_softmax_fwd(S.data_ptr(), optf(mask), P.data_ptr(), optp(Pd), rows, Sk, (int)rows_per_batch, (float)scale,
                       (float)p, (unsigned long long)seed, cs()),
      "softmax_fwd");
@@ -222,8 +265,10 @@ void softmax_fwd(at::Tensor S, c10::optional<at::Tensor> mask, at::Tensor P, c10
 
 void softmax_bwd(at::Tensor dPd, at::Tensor P, at::Tensor dS, double scale, double p, int64_t seed) {
   req(dPd, at::kBFloat16, "dPd"); req(P, at::kBFloat16, "P"); req(dS, at::kBFloat16, "dS");
-  const int Sk = (int)P.size(-1);
+  const int Sk = width_of(P, "softmax_bwd");
   const int rows = (int)(P.numel() / Sk);
+  need(dPd.numel() == P.numel() && dS.numel() == P.numel(), "softmax_bwd: dPd / dS size");
+  need_p(p, "softmax_bwd");
   ck(dtfk_softmax_bwd(dPd.data_ptr(), P.data_ptr(), dS.data_ptr(), rows, Sk, (float)scale, (float)p,
                       (unsigned long long)seed, cs()),
      "softmax_bwd");
@@ -232,6 +277,8 @@ void softmax_bwd(at::Tensor dPd, at::Tensor P, at::Tensor dS, double scale, doub
 void dropout_bf16(at::Tensor x, at::Tensor y, double p, int64_t seed) {
   req(x, at::kBFloat16, "x"); req(y, at::kBFloat16, "y");
   if (x.numel() % 4) throw std::runtime_error("dropout_bf16: numel % 4 != 0");
+  need(y.numel() == x.numel(), "dropout_bf16: y size");
+  need_p(p, "dropout_bf16");
   ck(dtfk_dropout_bf16(x.data_ptr(), y.data_ptr(), x.numel(), (float)p, (unsigned long long)seed, cs()), "dropout");
 }
 
