@@ -1,70 +1,14 @@
 // Python bindings for the fused NHWC BatchNorm(+residual)(+ReLU) kernels (csrc/kernels/bn.hip).
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
+#include "bind_common.h"
+#include "kernels/bn_api.h"
+#include "kernels/conv_igemm_api.h"
+#include "kernels/pool_api.h"
 
 #include <cstdlib>
-
-#include <stdexcept>
-#include <string>
 #include <tuple>
-
-extern "C" {
-int dtfk_bn_partial_rows(int M, int C);
-hipError_t dtfk_bn_fwd(const void* x, const void* res, const float* gamma, const float* beta, void* y, float* part,
-                       float* mean, float* invstd, float* scale, float* shift, float* run_mean, float* run_var,
-                       int M, int C, float momentum, float eps, int relu, hipStream_t st);
-hipError_t dtfk_bn_apply(const void* x, const void* res, const float* scale, const float* shift, void* y, int M, int C,
-                         int relu, hipStream_t st);
-hipError_t dtfk_bn_bwd(const void* dy, const void* x, const void* res, const float* gamma, const float* mean,
-                       const float* invstd, const float* scale, const float* shift, float* part, float* coef,
-                       void* dx, void* dres, float* dgamma, float* dbeta, int M, int C, int relu, int accum,
-                       int write_g, hipStream_t st);
-hipError_t dtfk_strided_add(void* full, const void* comp, int N, int H, int W, int C, int Ho, int Wo, int s,
-                            hipStream_t st);
-hipError_t dtfk_maxpool_fwd(const void* x, void* y, void* idx, int N, int H, int W, int C, int Ho, int Wo, int k,
-                            int s, int p, hipStream_t st);
-hipError_t dtfk_maxpool_bwd(const void* dy, const void* idx, void* dx, int N, int H, int W, int C, int Ho, int Wo,
-                            int k, int s, int p, hipStream_t st);
-int dtfk_conv3x3_supported(int N, int H, int W, int C, int K, int stride);
-hipError_t dtfk_conv3x3_fwd(const void* x, const void* w, void* y, float* part, int N, int H, int W, int C, int K,
-                            int stride, int bn, hipStream_t stream);
-long long dtfk_conv3x3_tiles(int N, int H, int W, int stride);
-hipError_t dtfk_conv3x3_wflip(const void* w, void* wt, int K, int C, hipStream_t stream);
-hipError_t dtfk_conv3x3_wgrad(const void* dy, const void* x, float* dw, float* ws, int N, int H, int W, int C, int K,
-                              int stride, int kcrs, hipStream_t stream);
-long long dtfk_conv3x3_wgrad_plan(int N, int H, int W, int C, int K, int stride, int* splits_out, int* sps_out);
-int dtfk_conv_supported(int N, int H, int W, int C, int K, int stride, int ks);
-hipError_t dtfk_conv_fwd(const void* x, const void* w, void* y, float* part, int N, int H, int W, int C, int K,
-                         int stride, int bn, int ks, int accum, const void* bnx, const float* bnst,
-                         const void* bnres, hipStream_t stream);
-hipError_t dtfk_bn_bwd_parts(const void* g, const void* x, const float* gamma, const float* mean, const float* invstd,
-                             const float* part, int P, float* coef, void* dx, float* dgamma, float* dbeta, int M, int C,
-                             int accum, hipStream_t st);
-long long dtfk_conv_tiles(int N, int H, int W, int stride, int ks);
-hipError_t dtfk_conv_wflip(const void* w, void* wt, int K, int C, int ks, hipStream_t stream);
-hipError_t dtfk_conv_wflip_multi(const long long* tab, const int* tiles, int ntiles, hipStream_t stream);
-long long dtfk_conv_wgrad_plan(int N, int H, int W, int C, int K, int stride, int ks, int* splits_out, int* sps_out);
-hipError_t dtfk_conv_wgrad(const void* dy, const void* x, float* dw, float* ws, int N, int H, int W, int C, int K,
-                           int stride, int ks, int kcrs, hipStream_t stream);
-long long dtfk_conv_wgrad_launch_plan(int N, int H, int W, int C, int K, int stride, int ks, int out[6]);
-long long dtfk_conv3x3_dx2_tiles(int N, int H, int W);
-int dtfk_conv3x3_dx2_supported(int N, int H, int W, int C, int K);
-hipError_t dtfk_conv3x3_dx2(const void* dy, const void* wt, void* dx, float* part, int N, int H, int W, int C, int K,
-                            int bn, int accum, const void* bnx, const float* bnst, hipStream_t stream);
-hipError_t dtfk_bn_stat_partials(const void* x, float* part, int M, int C, hipStream_t st);
-hipError_t dtfk_bn_fwd_parts(const void* x, const void* res, const float* gamma, const float* beta, void* y,
-                             const float* part, int P, float* mean, float* invstd, float* scale, float* shift,
-                             float* run_mean, float* run_var, int M, int C, float momentum, float eps, int relu,
-                             hipStream_t st);
-}
 
 namespace dtf {
 namespace {
-hipStream_t cs() { return c10::hip::getCurrentHIPStream().stream(); }
-void ck(hipError_t e, const char* w) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(w) + ": " + hipGetErrorString(e));
-}
 // NHWC bf16 activation viewed as [M, C]: channels_last 4-D or plain 2-D row-major
 int64_t rows_of(const at::Tensor& t, int64_t C) {
   if (!t.is_cuda() || t.scalar_type() != at::kBFloat16) throw std::runtime_error("bn: bf16 GPU activations");
@@ -73,11 +17,6 @@ int64_t rows_of(const at::Tensor& t, int64_t C) {
   if (!ok) throw std::runtime_error("bn: activation must be channels_last NCHW (or [M, C]) with C channels");
   return t.numel() / C;
 }
-void f32(const at::Tensor& t, int64_t n, const char* w) {
-  if (!t.is_cuda() || t.scalar_type() != at::kFloat || !t.is_contiguous() || t.numel() < n)
-    throw std::runtime_error(std::string("bn: ") + w + " must be a contiguous fp32 GPU tensor");
-}
-float* optf(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr<float>() : nullptr; }
 }  // namespace
 
 // ---- NHWC bf16 max pooling (kernels/pool.hip); idx: uint8 window position of each output's max
@@ -96,9 +35,9 @@ void maxpool_fwd(at::Tensor x, at::Tensor y, at::Tensor idx, int64_t k, int64_t 
   if (k < 1 || k * k > 255 || s < 1 || p < 0 || 2 * p > k) throw std::runtime_error("maxpool_fwd: window");
   if (!idx.is_cuda() || idx.scalar_type() != at::kByte || idx.numel() != y.numel())
     throw std::runtime_error("maxpool_fwd: idx must be a uint8 GPU tensor like y");
-  ck(dtfk_maxpool_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
-                      (int)k, (int)s, (int)p, cs()),
-     "maxpool_fwd");
+  hip_check(dtfk_maxpool_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)Ho,
+                             (int)Wo, (int)k, (int)s, (int)p, cur_stream()),
+            "maxpool_fwd");
 }
 
 void maxpool_bwd(at::Tensor dy, at::Tensor idx, at::Tensor dx, int64_t k, int64_t s, int64_t p) {
@@ -109,9 +48,9 @@ void maxpool_bwd(at::Tensor dy, at::Tensor idx, at::Tensor dx, int64_t k, int64_
     throw std::runtime_error("maxpool_bwd: shapes");
   if (!idx.is_cuda() || idx.scalar_type() != at::kByte || idx.numel() != dy.numel())
     throw std::runtime_error("maxpool_bwd: idx must be a uint8 GPU tensor like dy");
-  ck(dtfk_maxpool_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
-                      (int)k, (int)s, (int)p, cs()),
-     "maxpool_bwd");
+  hip_check(dtfk_maxpool_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)Ho,
+                             (int)Wo, (int)k, (int)s, (int)p, cur_stream()),
+            "maxpool_bwd");
 }
 
 int64_t bn_partial_rows(int64_t M, int64_t C) { return dtfk_bn_partial_rows((int)M, (int)C); }
@@ -123,13 +62,14 @@ void bn_fwd(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor gamma, at::T
   const int64_t M = rows_of(x, C);
   if (rows_of(y, C) != M) throw std::runtime_error("bn_fwd: y shape");
   if (res.has_value() && rows_of(*res, C) != M) throw std::runtime_error("bn_fwd: residual shape");
-  f32(gamma, C, "gamma"); f32(beta, C, "beta"); f32(stats, 4 * C, "stats");
-  f32(part, 2 * (int64_t)dtfk_bn_partial_rows((int)M, (int)C) * C, "part");
+  need(gamma, at::kFloat, C, "gamma"); need(beta, at::kFloat, C, "beta"); need(stats, at::kFloat, 4 * C, "stats");
+  need(part, at::kFloat, 2 * (int64_t)dtfk_bn_partial_rows((int)M, (int)C) * C, "part");
   float* s = stats.data_ptr<float>();
-  ck(dtfk_bn_fwd(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, gamma.data_ptr<float>(),
-                 beta.data_ptr<float>(), y.data_ptr(), part.data_ptr<float>(), s, s + C, s + 2 * C, s + 3 * C,
-                 optf(run_mean), optf(run_var), (int)M, (int)C, (float)momentum, (float)eps, relu ? 1 : 0, cs()),
-     "bn_fwd");
+  hip_check(dtfk_bn_fwd(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, gamma.data_ptr<float>(),
+                        beta.data_ptr<float>(), y.data_ptr(), part.data_ptr<float>(), s, s + C, s + 2 * C, s + 3 * C,
+                        opt_ptr<float>(run_mean), opt_ptr<float>(run_var), (int)M, (int)C, (float)momentum, (float)eps,
+                        relu ? 1 : 0, cur_stream()),
+            "bn_fwd");
 }
 
 // bn_fwd with the statistics partials [2, P, C] supplied by the producer of x
@@ -140,22 +80,23 @@ void bn_fwd_parts(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor gamma,
   const int64_t M = rows_of(x, C);
   if (rows_of(y, C) != M) throw std::runtime_error("bn_fwd_parts: y shape");
   if (res.has_value() && rows_of(*res, C) != M) throw std::runtime_error("bn_fwd_parts: residual shape");
-  f32(gamma, C, "gamma"); f32(beta, C, "beta"); f32(stats, 4 * C, "stats"); f32(part, 2 * P * C, "part");
+  need(gamma, at::kFloat, C, "gamma"); need(beta, at::kFloat, C, "beta"); need(stats, at::kFloat, 4 * C, "stats");
+  need(part, at::kFloat, 2 * P * C, "part");
   float* s = stats.data_ptr<float>();
-  ck(dtfk_bn_fwd_parts(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, gamma.data_ptr<float>(),
-                       beta.data_ptr<float>(), y.data_ptr(), part.data_ptr<float>(), (int)P, s, s + C, s + 2 * C,
-                       s + 3 * C, optf(run_mean), optf(run_var), (int)M, (int)C, (float)momentum, (float)eps,
-                       relu ? 1 : 0, cs()),
-     "bn_fwd_parts");
+  hip_check(dtfk_bn_fwd_parts(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, gamma.data_ptr<float>(),
+                              beta.data_ptr<float>(), y.data_ptr(), part.data_ptr<float>(), (int)P, s, s + C, s + 2 * C,
+                              s + 3 * C, opt_ptr<float>(run_mean), opt_ptr<float>(run_var), (int)M, (int)C,
+                              (float)momentum, (float)eps, relu ? 1 : 0, cur_stream()),
+            "bn_fwd_parts");
 }
 
 void bn_apply(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor scale, at::Tensor shift, at::Tensor y,
               bool relu) {
   const int64_t C = scale.numel();
   const int64_t M = rows_of(x, C);
-  ck(dtfk_bn_apply(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, scale.data_ptr<float>(),
-                   shift.data_ptr<float>(), y.data_ptr(), (int)M, (int)C, relu ? 1 : 0, cs()),
-     "bn_apply");
+  hip_check(dtfk_bn_apply(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, scale.data_ptr<float>(),
+                          shift.data_ptr<float>(), y.data_ptr(), (int)M, (int)C, relu ? 1 : 0, cur_stream()),
+            "bn_apply");
 }
 
 void bn_bwd(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> res, at::Tensor gamma, at::Tensor stats,
@@ -165,8 +106,9 @@ void bn_bwd(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> res, at::Tens
   const int64_t M = rows_of(x, C);
   if (rows_of(dy, C) != M || rows_of(dx, C) != M) throw std::runtime_error("bn_bwd: shapes");
   if (res.has_value() != dres.has_value()) throw std::runtime_error("bn_bwd: res and dres go together");
-  f32(stats, 4 * C, "stats"); f32(coef, 3 * C, "coef"); f32(dgamma, C, "dgamma"); f32(dbeta, C, "dbeta");
-  f32(part, 2 * (int64_t)dtfk_bn_partial_rows((int)M, (int)C) * C, "part");
+  need(stats, at::kFloat, 4 * C, "stats"); need(coef, at::kFloat, 3 * C, "coef"); need(dgamma, at::kFloat, C, "dgamma");
+  need(dbeta, at::kFloat, C, "dbeta");
+  need(part, at::kFloat, 2 * (int64_t)dtfk_bn_partial_rows((int)M, (int)C) * C, "part");
   const float* s = stats.data_ptr<float>();
   // residual + ReLU blocks: the partials pass stores g = dres and the apply pass reads
   // (g, x) -- one tensor pass fewer (DTF_BN_WRITE_G=0: recompute g from dy, x, res twice)
@@ -174,11 +116,12 @@ void bn_bwd(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> res, at::Tens
     const char* e = getenv("DTF_BN_WRITE_G");
     return e == nullptr || e[0] != '0';
   }();
-  ck(dtfk_bn_bwd(dy.data_ptr(), x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, gamma.data_ptr<float>(),
-                 s, s + C, s + 2 * C, s + 3 * C, part.data_ptr<float>(), coef.data_ptr<float>(), dx.data_ptr(),
-                 dres.has_value() ? dres->data_ptr() : nullptr, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                 (int)M, (int)C, relu ? 1 : 0, accum ? 1 : 0, write_g ? 1 : 0, cs()),
-     "bn_bwd");
+  hip_check(dtfk_bn_bwd(dy.data_ptr(), x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr,
+                        gamma.data_ptr<float>(), s, s + C, s + 2 * C, s + 3 * C, part.data_ptr<float>(),
+                        coef.data_ptr<float>(), dx.data_ptr(), dres.has_value() ? dres->data_ptr() : nullptr,
+                        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), (int)M, (int)C, relu ? 1 : 0, accum ? 1 : 0,
+                        write_g ? 1 : 0, cur_stream()),
+            "bn_bwd");
 }
 
 // full[:, :, s*i, s*j] += comp (channels_last bf16 [N, C, H, W] and [N, C, Ho, Wo])
@@ -188,9 +131,9 @@ void strided_add(at::Tensor full, at::Tensor comp, int64_t s) {
         !t->is_contiguous(at::MemoryFormat::ChannelsLast))
       throw std::runtime_error("strided_add: channels_last bf16 4-D CUDA tensors");
   if (full.size(0) != comp.size(0) || full.size(1) != comp.size(1)) throw std::runtime_error("strided_add: N / C differ");
-  ck(dtfk_strided_add(full.data_ptr(), comp.data_ptr(), (int)full.size(0), (int)full.size(2), (int)full.size(3),
-                      (int)full.size(1), (int)comp.size(2), (int)comp.size(3), (int)s, cs()),
-     "strided_add");
+  hip_check(dtfk_strided_add(full.data_ptr(), comp.data_ptr(), (int)full.size(0), (int)full.size(2), (int)full.size(3),
+                             (int)full.size(1), (int)comp.size(2), (int)comp.size(3), (int)s, cur_stream()),
+            "strided_add");
 }
 
 // 3x3 (pad 1) or 1x1 (pad 0), stride 1 or 2 convolution on channels_last bf16
@@ -254,7 +197,7 @@ void conv3x3_fwd(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Ten
     cl_bf16(*bn_x, "conv_fwd bn_x");
     if (!bn_stats.has_value() || pp == nullptr || accumulate != bn_res.has_value() || bn_x->sizes() != y.sizes())
       throw std::runtime_error("conv_fwd: bn_x needs bn_stats, part, y's shape, and accumulate iff bn_res");
-    f32(*bn_stats, 4LL * K, "bn_stats");
+    need(*bn_stats, at::kFloat, 4LL * K, "bn_stats");
     bx = bn_x->data_ptr();
     bst = bn_stats->data_ptr<float>();
     if (bn_res.has_value()) {
@@ -268,9 +211,9 @@ void conv3x3_fwd(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Ten
     // the statistics epilogue sums the convolution alone, not the stored y + conv
     throw std::runtime_error("conv_fwd: part with accumulate needs bn_x (statistics of y + conv are not computed)");
   }
-  ck(dtfk_conv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), pp, N, H, W, C, K, (int)stride, (int)bn, ks,
-                   accumulate ? 1 : 0, bx, bst, br, cs()),
-     "conv_fwd");
+  hip_check(dtfk_conv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), pp, N, H, W, C, K, (int)stride, (int)bn, ks,
+                          accumulate ? 1 : 0, bx, bst, br, cur_stream()),
+            "conv_fwd");
 }
 
 // Input gradient of y = conv2d(x, w, stride 2, padding 1), w 3x3: dy [N, K, Ho, Wo],
@@ -308,15 +251,15 @@ void conv3x3_dx2(at::Tensor dy, at::Tensor wt, at::Tensor dx, c10::optional<at::
     cl_bf16(*bn_x, "conv3x3_dx2 bn_x");
     if (!bn_stats.has_value() || pp == nullptr || accumulate || bn_x->sizes() != dx.sizes())
       throw std::runtime_error("conv3x3_dx2: bn_x needs bn_stats, part and dx's shape, and no accumulate");
-    f32(*bn_stats, 4LL * C, "bn_stats");
+    need(*bn_stats, at::kFloat, 4LL * C, "bn_stats");
     bx = bn_x->data_ptr();
     bst = bn_stats->data_ptr<float>();
   } else if (pp != nullptr) {
     throw std::runtime_error("conv3x3_dx2: part needs bn_x");
   }
-  ck(dtfk_conv3x3_dx2(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), pp, N, H, W, C, K, (int)bn, accumulate ? 1 : 0, bx,
-                      bst, cs()),
-     "conv3x3_dx2");
+  hip_check(dtfk_conv3x3_dx2(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), pp, N, H, W, C, K, (int)bn,
+                             accumulate ? 1 : 0, bx, bst, cur_stream()),
+            "conv3x3_dx2");
 }
 
 // wt [C, K, ks, ks] channels_last = the flipped, transposed filter of the stride-1 input gradient
@@ -326,7 +269,8 @@ void conv3x3_wflip(at::Tensor w, at::Tensor wt) {
   const int ks = ksize(w);
   if (ks == 0 || wt.size(0) != w.size(1) || wt.size(1) != w.size(0) || wt.size(2) != ks || wt.size(3) != ks)
     throw std::runtime_error("conv_wflip: shapes");
-  ck(dtfk_conv_wflip(w.data_ptr(), wt.data_ptr(), (int)w.size(0), (int)w.size(1), ks, cs()), "conv_wflip");
+  hip_check(dtfk_conv_wflip(w.data_ptr(), wt.data_ptr(), (int)w.size(0), (int)w.size(1), ks, cur_stream()),
+            "conv_wflip");
 }
 
 // Several filters flipped in one launch.  tab: int64 [n, 5] rows {w, wt, K, C, ks}
@@ -338,9 +282,9 @@ void conv_wflip_multi(at::Tensor tab, at::Tensor tiles) {
       !tiles.is_cuda() || tiles.scalar_type() != at::kInt || tiles.dim() != 2 || tiles.size(1) != 4 ||
       !tiles.is_contiguous())
     throw std::runtime_error("conv_wflip_multi: tab int64 [n, 5], tiles int32 [m, 4] on the device");
-  ck(dtfk_conv_wflip_multi(reinterpret_cast<const long long*>(tab.data_ptr<int64_t>()), tiles.data_ptr<int>(),
-                           (int)tiles.size(0), cs()),
-     "conv_wflip_multi");
+  hip_check(dtfk_conv_wflip_multi(reinterpret_cast<const long long*>(tab.data_ptr<int64_t>()), tiles.data_ptr<int>(),
+                                  (int)tiles.size(0), cur_stream()),
+            "conv_wflip_multi");
 }
 
 // dw (fp32 [K, C, ks, ks], channels_last or contiguous) += the weight gradient of
@@ -366,9 +310,9 @@ void conv3x3_wgrad(at::Tensor dy, at::Tensor x, at::Tensor dw, int64_t stride) {
   const long long wsn = dtfk_conv_wgrad_plan(N, H, W, C, K, (int)stride, ks, nullptr, nullptr);
   at::Tensor ws;
   if (wsn > 0) ws = at::empty({wsn}, dw.options());
-  ck(dtfk_conv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(), wsn > 0 ? ws.data_ptr<float>() : nullptr, N,
-                     H, W, C, K, (int)stride, ks, kcrs, cs()),
-     "conv_wgrad");
+  hip_check(dtfk_conv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(), wsn > 0 ? ws.data_ptr<float>() : nullptr,
+                            N, H, W, C, K, (int)stride, ks, kcrs, cur_stream()),
+            "conv_wgrad");
 }
 
 // The launch plan dtfk_conv_wgrad uses for this shape (read-only): (splits,
@@ -394,13 +338,14 @@ void bn_bwd_parts(at::Tensor g, at::Tensor x, at::Tensor gamma, at::Tensor stats
   const int64_t C = gamma.numel();
   const int64_t M = rows_of(x, C);
   if (rows_of(g, C) != M || rows_of(dx, C) != M) throw std::runtime_error("bn_bwd_parts: shapes");
-  f32(stats, 4 * C, "stats"); f32(coef, 3 * C, "coef"); f32(dgamma, C, "dgamma"); f32(dbeta, C, "dbeta");
-  f32(part, 2 * P * C, "part");
+  need(stats, at::kFloat, 4 * C, "stats"); need(coef, at::kFloat, 3 * C, "coef"); need(dgamma, at::kFloat, C, "dgamma");
+  need(dbeta, at::kFloat, C, "dbeta");
+  need(part, at::kFloat, 2 * P * C, "part");
   const float* s = stats.data_ptr<float>();
-  ck(dtfk_bn_bwd_parts(g.data_ptr(), x.data_ptr(), gamma.data_ptr<float>(), s, s + C, part.data_ptr<float>(), (int)P,
-                       coef.data_ptr<float>(), dx.data_ptr(), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                       (int)M, (int)C, accum ? 1 : 0, cs()),
-     "bn_bwd_parts");
+  hip_check(dtfk_bn_bwd_parts(g.data_ptr(), x.data_ptr(), gamma.data_ptr<float>(), s, s + C, part.data_ptr<float>(),
+                              (int)P, coef.data_ptr<float>(), dx.data_ptr(), dgamma.data_ptr<float>(),
+                              dbeta.data_ptr<float>(), (int)M, (int)C, accum ? 1 : 0, cur_stream()),
+            "bn_bwd_parts");
 }
 
 // BatchNorm statistics partials of x alone ([2, P, C], P = bn_partial_rows(M, C));
@@ -410,8 +355,9 @@ int64_t bn_stat_partials(at::Tensor x, at::Tensor part) {
   const int64_t C = x.dim() == 4 ? x.size(1) : x.size(1);
   const int64_t M = rows_of(x, C);
   const int P = dtfk_bn_partial_rows((int)M, (int)C);
-  f32(part, 2LL * P * C, "part");
-  ck(dtfk_bn_stat_partials(x.data_ptr(), part.data_ptr<float>(), (int)M, (int)C, cs()), "bn_stat_partials");
+  need(part, at::kFloat, 2LL * P * C, "part");
+  hip_check(dtfk_bn_stat_partials(x.data_ptr(), part.data_ptr<float>(), (int)M, (int)C, cur_stream()),
+            "bn_stat_partials");
   return P;
 }
 

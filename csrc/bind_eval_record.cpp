@@ -1,14 +1,8 @@
 // eval_record_reduce: the evaluation record's reduce kernel
 // (csrc/kernels/eval_record.hip) on per-row arrays the caller supplies, without
 // a model's rows kernel in front of it.
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
-
+#include "bind_common.h"
 #include "eval_record_host.h"
-
-#include <stdexcept>
-#include <string>
 
 namespace dtf {
 
@@ -26,10 +20,9 @@ static void eval_record_reduce(at::Tensor lrow, at::Tensor prow, at::Tensor brow
   TORCH_CHECK(B >= 1 && B <= (1 << 30) && prow.numel() == B && brow.numel() == B && labels.numel() == B, who,
               ": the four row arrays must hold the same 1 <= B <= 2^30 entries");
   const EvalOut o = eval_out(who, dev, B, record, reset, c10::nullopt, c10::nullopt);
-  const hipError_t e = dtfk_eval_reduce(lrow.data_ptr<float>(), prow.data_ptr<float>(), brow.data_ptr<int>(),
-                                        labels.data_ptr<float>(), (int)B, o.T, o.reset, o.rec,
-                                        c10::hip::getCurrentHIPStream().stream());
-  if (e != hipSuccess) throw std::runtime_error(std::string(who) + ": " + hipGetErrorString(e));
+  hip_check(dtfk_eval_reduce(lrow.data_ptr<float>(), prow.data_ptr<float>(), brow.data_ptr<int>(),
+                             labels.data_ptr<float>(), (int)B, o.T, o.reset, o.rec, cur_stream()),
+            who);
 }
 
 void init_eval_record(py::module& m) {

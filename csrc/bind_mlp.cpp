@@ -1,13 +1,11 @@
 // Python bindings for the fused MLP step kernels (csrc/kernels/mlp_step.hip)
 // and the pinned-host -> device batch copy used by the input pipeline.
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <pybind11/numpy.h>
-#include <hip/hip_runtime.h>
-
+#include "bind_common.h"
 #include "comm/ipc_coll_host.h"
 #include "gstep_host.h"
 #include "kernels/mlp_api.h"
+
+#include <pybind11/numpy.h>
 
 #include <algorithm>
 #include <atomic>
@@ -18,21 +16,6 @@
 #include <string>
 
 namespace dtf {
-
-static hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-static void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-static void need(const at::Tensor& t, at::ScalarType dt, int64_t numel, const char* name) {
-  if (!t.is_cuda()) throw std::runtime_error(std::string(name) + " must be a GPU tensor");
-  if (!t.is_contiguous()) throw std::runtime_error(std::string(name) + " must be contiguous");
-  if (t.scalar_type() != dt) throw std::runtime_error(std::string(name) + " has wrong dtype");
-  if (numel >= 0 && t.numel() < numel)
-    throw std::runtime_error(std::string(name) + " too small: " + std::to_string(t.numel()) +
-                             " < " + std::to_string(numel));
-}
 
 constexpr int kNParam = 79510;
 

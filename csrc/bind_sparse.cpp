@@ -18,13 +18,12 @@
 // (slr_eval_rows + the record's reduce, eval_record.hip) of device tensors /
 // the same host feeds: packing, int32 ids and the two staging slots are the training step's
 // (submit_), the kernels read W and b only and add the batch to a device record.
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <pybind11/numpy.h>
-#include <hip/hip_runtime.h>
-
+#include "bind_common.h"
 #include "eval_record_host.h"
 #include "gstep_host.h"
+#include "kernels/sparse_lr_api.h"
+
+#include <pybind11/numpy.h>
 
 #include <chrono>
 #include <cstdlib>
@@ -33,38 +32,7 @@
 #include <string>
 #include <vector>
 
-extern "C" {
-hipError_t dtfk_slr_step(float* W, long long F, const void* ids, int ids32, const long long* offsets,
-                         const float* vals, const float* labels, float* bias, int B, const float* lr_ptr, float lr_val,
-                         float* dz, float* lrow, float* loss_out, int* bad, void* gvar, int gkind, hipStream_t stream);
-hipError_t dtfk_slr_stage(const void* src, void* dst, long long bytes, hipStream_t stream);
-void dtfk_slr_set_rows_per_wg(int rpw);
-hipError_t dtfk_slr_step_direct(float* W, long long F, const void* hids, int ids32, const long long* hoffsets,
-                                const float* hvals, const float* hlabels, void* ids_d, long long* off_d, float* vals_d,
-                                float* bias, int B, float lr_val, float* dz, float* lrow, float* loss_out, int* bad,
-                                void* gvar, int gkind, hipStream_t stream);
-hipError_t dtfk_slr_ftrl_step(float* W, long long F, const void* ids, int ids32, const long long* offsets,
-                              const float* vals, const float* labels, float* bias, int B, const float* lr_ptr,
-                              float lr_val, float* dz, float* lrow, float* loss_out, int* bad, void* gvar, int gkind,
-                              float* acc, float* lin, float* gsum, float* bslots, float lr_power, float l1, float l2,
-                              float shrink, hipStream_t stream);
-hipError_t dtfk_slr_ftrl_step_direct(float* W, long long F, const void* hids, int ids32, const long long* hoffsets,
-                                     const float* hvals, const float* hlabels, void* ids_d, long long* off_d,
-                                     float* vals_d, float* bias, int B, float lr_val, float* dz, float* lrow,
-                                     float* loss_out, int* bad, void* gvar, int gkind, float* acc, float* lin,
-                                     float* gsum, float* bslots, float lr_power, float l1, float l2, float shrink,
-                                     hipStream_t stream);
-hipError_t dtfk_slr_eval(const float* W, long long F, const void* ids, int ids32, const long long* offsets,
-                         const float* vals, const float* labels, float* labels_d, int direct, const float* bias, int B,
-                         float* lrow, float* prow, int* brow, int* bad, float* z_out, float* p_out, int T, int reset,
-                         long long* rec, hipStream_t stream);
-}
-
 namespace dtf {
-
-static void hck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 
 static int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
 
@@ -82,7 +50,7 @@ class SparseLRPlan {
     auto fo = W.options();
     loss_ = at::zeros({1}, fo);
     bad_ = at::zeros({1}, fo.dtype(at::kInt));
-    for (int i = 0; i < 2; ++i) hck(hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming), "hipEventCreate");
+    for (int i = 0; i < 2; ++i) hip_check(hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming), "hipEventCreate");
     const char* fe = std::getenv("DTF_SLR_FEED");
     const std::string f = fe != nullptr ? fe : "direct";
     feed_ = f == "dma" ? 2 : (f == "stage" ? 1 : (f == "overlap" ? 3 : 0));
@@ -97,9 +65,9 @@ class SparseLRPlan {
       std::vector<uint32_t> mask((size_t)std::max(1, (ncu + 31) / 32), 0xffffffffu);
       if (ncu <= 0 || hipExtStreamCreateWithCUMask(&side_, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
         (void)hipGetLastError();
-        hck(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking), "SparseLRPlan: side stream");
+        hip_check(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking), "SparseLRPlan: side stream");
       }
-      for (int i = 0; i < 2; ++i) hck(hipEventCreateWithFlags(&evs_[i], hipEventDisableTiming), "hipEventCreate");
+      for (int i = 0; i < 2; ++i) hip_check(hipEventCreateWithFlags(&evs_[i], hipEventDisableTiming), "hipEventCreate");
     }
   }
   ~SparseLRPlan() {
@@ -338,21 +306,21 @@ class SparseLRPlan {
     else esc_.ensure(B, W_.options());
     at::Tensor& dvb = feed_ == 3 ? dev2_[slot] : dev_;   // overlap: one device copy per slot
     if (dvb.numel() < total) dvb = at::empty({std::max<int64_t>(total, 1 << 20)}, W_.options().dtype(at::kByte));
-    hipStream_t st = c10::hip::getCurrentHIPStream().stream();
+    hipStream_t st = cur_stream();
     f.d = static_cast<char*>(dvb.data_ptr());
     {
       py::gil_scoped_release nogil;
       using clk = std::chrono::steady_clock;
       const auto t0 = clk::now();
-      if (pending_[slot]) hck(hipEventSynchronize(ev_[slot]), "SparseLRPlan: staging slot");
+      if (pending_[slot]) hip_check(hipEventSynchronize(ev_[slot]), "SparseLRPlan: staging slot");
       pending_[slot] = false;
       if (hcap_[slot] < total) {   // mapped + coherent: the staging kernel reads it in place
-        if (hbuf_[slot]) hck(hipHostFree(hbuf_[slot]), "hipHostFree");
+        if (hbuf_[slot]) hip_check(hipHostFree(hbuf_[slot]), "hipHostFree");
         hbuf_[slot] = nullptr;
         const int64_t cap = std::max<int64_t>(total, 1 << 20);
-        hck(hipHostMalloc(&hbuf_[slot], (size_t)cap, hipHostMallocMapped | hipHostMallocCoherent),
-            "SparseLRPlan: pinned staging slot");
-        hck(hipHostGetDevicePointer(&hdev_[slot], hbuf_[slot], 0), "SparseLRPlan: staging slot device view");
+        hip_check(hipHostMalloc(&hbuf_[slot], (size_t)cap, hipHostMallocMapped | hipHostMallocCoherent),
+                  "SparseLRPlan: pinned staging slot");
+        hip_check(hipHostGetDevicePointer(&hdev_[slot], hbuf_[slot], 0), "SparseLRPlan: staging slot device view");
         hcap_[slot] = cap;
       }
       const auto tw = clk::now();   // slot wait (+ first-use allocation) | packing
@@ -389,39 +357,43 @@ class SparseLRPlan {
       // the forward kernel reads the slot in place and leaves device copies for the apply
       const char* hd = f.hd;
       if (ftrl_) {
-        hck(dtfk_slr_ftrl_step_direct(
-                W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
-                reinterpret_cast<const long long*>(hd + o_off), reinterpret_cast<const float*>(hd + o_val),
-                reinterpret_cast<const float*>(hd + o_lab), d + o_ids, reinterpret_cast<long long*>(d + o_off),
-                reinterpret_cast<float*>(d + o_val), bias_.data_ptr<float>(), B, (float)lr,
-                dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
-                gs_.ptr, gs_.kind, acc_.data_ptr<float>(), lin_.data_ptr<float>(), gsum_.data_ptr<float>(),
-                bslots_.data_ptr<float>(), hp_[0], hp_[1], hp_[2], hp_[3], st),
-            "SparseLRPlan: FTRL step");
+        hip_check(dtfk_slr_ftrl_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
+                                            reinterpret_cast<const long long*>(hd + o_off),
+                                            reinterpret_cast<const float*>(hd + o_val),
+                                            reinterpret_cast<const float*>(hd + o_lab), d + o_ids,
+                                            reinterpret_cast<long long*>(d + o_off),
+                                            reinterpret_cast<float*>(d + o_val), bias_.data_ptr<float>(), B, (float)lr,
+                                            dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(),
+                                            bad_.data_ptr<int>(), gs_.ptr, gs_.kind, acc_.data_ptr<float>(),
+                                            lin_.data_ptr<float>(), gsum_.data_ptr<float>(), bslots_.data_ptr<float>(),
+                                            hp_[0], hp_[1], hp_[2], hp_[3], st),
+                  "SparseLRPlan: FTRL step");
       } else {
-        hck(dtfk_slr_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
-                                 reinterpret_cast<const long long*>(hd + o_off),
-                                 reinterpret_cast<const float*>(hd + o_val), reinterpret_cast<const float*>(hd + o_lab),
-                                 d + o_ids, reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
-                                 bias_.data_ptr<float>(), B, (float)lr, dz_.data_ptr<float>(),
-                                 lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(),
-                                 gs_.ptr, gs_.kind, st),
-            "SparseLRPlan: step");
+        hip_check(dtfk_slr_step_direct(W_.data_ptr<float>(), (long long)F_, hd + o_ids, i32 ? 1 : 0,
+                                       reinterpret_cast<const long long*>(hd + o_off),
+                                       reinterpret_cast<const float*>(hd + o_val),
+                                       reinterpret_cast<const float*>(hd + o_lab), d + o_ids,
+                                       reinterpret_cast<long long*>(d + o_off), reinterpret_cast<float*>(d + o_val),
+                                       bias_.data_ptr<float>(), B, (float)lr, dz_.data_ptr<float>(),
+                                       lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(), gs_.ptr,
+                                       gs_.kind, st),
+                  "SparseLRPlan: step");
       }
-      hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
+      hip_check(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
       pending_[slot] = true;
     } else if (feed_ == 3) {
-      hck(dtfk_slr_stage(f.hd, d, total, side_), "SparseLRPlan: feed staging");
-      hck(hipEventRecord(evs_[slot], side_), "SparseLRPlan: event");
-      hck(hipStreamWaitEvent(st, evs_[slot], 0), "SparseLRPlan: wait staging");
+      hip_check(dtfk_slr_stage(f.hd, d, total, side_), "SparseLRPlan: feed staging");
+      hip_check(hipEventRecord(evs_[slot], side_), "SparseLRPlan: event");
+      hip_check(hipStreamWaitEvent(st, evs_[slot], 0), "SparseLRPlan: wait staging");
       launch(d + o_ids, i32, reinterpret_cast<const long long*>(d + o_off), reinterpret_cast<const float*>(d + o_val),
              reinterpret_cast<const float*>(d + o_lab), B, (float)lr, st);
-      hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");   // host + device slot free after the step
+      hip_check(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");   // host + device slot free after the step
       pending_[slot] = true;
     } else {
-      if (feed_ == 2) hck(hipMemcpyAsync(d, f.h, (size_t)total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
-      else hck(dtfk_slr_stage(f.hd, d, total, st), "SparseLRPlan: feed staging");
-      hck(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
+      if (feed_ == 2)
+        hip_check(hipMemcpyAsync(d, f.h, (size_t)total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
+      else hip_check(dtfk_slr_stage(f.hd, d, total, st), "SparseLRPlan: feed staging");
+      hip_check(hipEventRecord(ev_[slot], st), "SparseLRPlan: event");
       pending_[slot] = true;
       launch(d + o_ids, i32, reinterpret_cast<const long long*>(d + o_off), reinterpret_cast<const float*>(d + o_val),
              reinterpret_cast<const float*>(d + o_lab), B, (float)lr, st);
@@ -432,24 +404,26 @@ class SparseLRPlan {
   // default feed mode; no staging copy), else staged on the caller's stream first
   void eval_go_(const Feed& f, const EvalOut& o, hipStream_t st) {
     const bool direct = feed_ == 0;
-    if (feed_ == 2) hck(hipMemcpyAsync(f.d, f.h, (size_t)f.total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
-    else if (!direct) hck(dtfk_slr_stage(f.hd, f.d, f.total, st), "SparseLRPlan: feed staging");
+    if (feed_ == 2)
+      hip_check(hipMemcpyAsync(f.d, f.h, (size_t)f.total, hipMemcpyHostToDevice, st), "SparseLRPlan: feed copy");
+    else if (!direct) hip_check(dtfk_slr_stage(f.hd, f.d, f.total, st), "SparseLRPlan: feed staging");
     const char* src = direct ? f.hd : f.d;
     eval_launch_(src + f.o_ids, f.i32, reinterpret_cast<const long long*>(src + f.o_off),
                  reinterpret_cast<const float*>(src + f.o_val), reinterpret_cast<const float*>(src + f.o_lab), direct,
                  f.B, o, st);
-    hck(hipEventRecord(ev_[f.slot], st), "SparseLRPlan: event");   // slot (and device copy) free after the kernels
+    // slot (and device copy) free after the kernels
+    hip_check(hipEventRecord(ev_[f.slot], st), "SparseLRPlan: event");
     pending_[f.slot] = true;
   }
 
   void eval_launch_(const void* ids, bool i32, const long long* offs, const float* vals, const float* labels,
                     bool direct, int B, const EvalOut& o, hipStream_t st) {
     // the scratch's quarters: lrow | prow | labels | bad ids per row (int)
-    hck(dtfk_slr_eval(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, esc_.part(2),
-                      direct ? 1 : 0, bias_.data_ptr<float>(), B, esc_.part(0), esc_.part(1),
-                      reinterpret_cast<int*>(esc_.part(3)), bad_.data_ptr<int>(), o.logits, o.pred, o.T, o.reset, o.rec,
-                      st),
-        "SparseLRPlan: evaluation");
+    hip_check(dtfk_slr_eval(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, esc_.part(2),
+                            direct ? 1 : 0, bias_.data_ptr<float>(), B, esc_.part(0), esc_.part(1),
+                            reinterpret_cast<int*>(esc_.part(3)), bad_.data_ptr<int>(), o.logits, o.pred, o.T, o.reset,
+                            o.rec, st),
+              "SparseLRPlan: evaluation");
   }
 
   void ensure_rows_(int64_t B) {
@@ -475,7 +449,7 @@ class SparseLRPlan {
     }
     ensure_rows_(B);
     launch(ids.data_ptr(), false, reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()), vp,
-           labels.data_ptr<float>(), (int)B, (float)lr, c10::hip::getCurrentHIPStream().stream());
+           labels.data_ptr<float>(), (int)B, (float)lr, cur_stream());
     ++runs_;
     return loss();
   }
@@ -492,7 +466,7 @@ class SparseLRPlan {
     const EvalOut o = eval_out("SparseLRPlan", dev, in.B, record, reset, pred, logits);
     esc_.ensure(in.B, W_.options());
     eval_launch_(in.ids, false, in.offsets, in.vals, in.labels, false, (int)in.B, o,
-                 c10::hip::getCurrentHIPStream().stream());
+                 cur_stream());
     ++eval_runs_;
   }
   int64_t eval_runs() const { return eval_runs_; }
@@ -518,18 +492,18 @@ class SparseLRPlan {
   void launch(const void* ids, bool i32, const long long* offs, const float* vals, const float* labels, int B,
               float lr, hipStream_t st) {
     if (ftrl_) {
-      hck(dtfk_slr_ftrl_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels,
-                             bias_.data_ptr<float>(), B, nullptr, lr, dz_.data_ptr<float>(), lrow_.data_ptr<float>(),
-                             loss_.data_ptr<float>(), bad_.data_ptr<int>(), gs_.ptr, gs_.kind, acc_.data_ptr<float>(),
-                             lin_.data_ptr<float>(), gsum_.data_ptr<float>(), bslots_.data_ptr<float>(), hp_[0], hp_[1],
-                             hp_[2], hp_[3], st),
-          "SparseLRPlan: FTRL step");
+      hip_check(dtfk_slr_ftrl_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels,
+                                   bias_.data_ptr<float>(), B, nullptr, lr, dz_.data_ptr<float>(),
+                                   lrow_.data_ptr<float>(), loss_.data_ptr<float>(), bad_.data_ptr<int>(), gs_.ptr,
+                                   gs_.kind, acc_.data_ptr<float>(), lin_.data_ptr<float>(), gsum_.data_ptr<float>(),
+                                   bslots_.data_ptr<float>(), hp_[0], hp_[1], hp_[2], hp_[3], st),
+                "SparseLRPlan: FTRL step");
       return;
     }
-    hck(dtfk_slr_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels, bias_.data_ptr<float>(), B, nullptr,
-                      lr, dz_.data_ptr<float>(), lrow_.data_ptr<float>(), loss_.data_ptr<float>(),
-                      bad_.data_ptr<int>(), gs_.ptr, gs_.kind, st),
-        "SparseLRPlan: step");
+    hip_check(dtfk_slr_step(W_.data_ptr<float>(), (long long)F_, ids, i32 ? 1 : 0, offs, vals, labels,
+                            bias_.data_ptr<float>(), B, nullptr, lr, dz_.data_ptr<float>(), lrow_.data_ptr<float>(),
+                            loss_.data_ptr<float>(), bad_.data_ptr<int>(), gs_.ptr, gs_.kind, st),
+              "SparseLRPlan: step");
   }
 
   at::Tensor W_, bias_, gstep_, loss_, bad_, dev_, dz_, lrow_;

@@ -1,73 +1,16 @@
 // Python bindings for the fused transformer kernels (csrc/kernels/transformer.hip).
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
-
-#include <stdexcept>
-#include <string>
-
-extern "C" {
-hipError_t dtfk_bdrln_fwd(const void* x, const float* bias, const void* res, const float* gamma, const float* beta,
-                          void* y, void* s_out, float* mean, float* rstd, int N, int H, float eps, float p,
-                          unsigned long long seed, hipStream_t st);
-hipError_t dtfk_emb_ln_fwd(const float* word, const int64_t* ids, const float* typ, const int64_t* tt,
-                           const float* pos, int S, const float* gamma, const float* beta, void* y, void* s_out,
-                           float* mean, float* rstd, int N, int H, float eps, float p, unsigned long long seed,
-                           hipStream_t st);
-hipError_t dtfk_emb_bwd_aux(const void* ds, const int64_t* tt, int B, int S, int H, float* pos_grad, float* part,
-                            int accumulate, hipStream_t st);
-hipError_t dtfk_ln_fwd_f32in(const float* x, const float* gamma, const float* beta, void* y, void* s_out,
-                             float* mean, float* rstd, int N, int H, float eps, float p, unsigned long long seed,
-                             hipStream_t st);
-hipError_t dtfk_ln_bwd(const void* dy, const void* s, const float* mean, const float* rstd, const float* gamma,
-                       void* ds, void* dxb, float* part_g, float* part_b, float* part_bias, int grid, int N, int H,
-                       float p, unsigned long long seed, hipStream_t st);
-hipError_t dtfk_colsum_partials(const float* part, float* out, int P, int H, hipStream_t st);
-hipError_t dtfk_colsum_partials_multi(const float* const* parts, float* const* outs, int nbuf, int P, int H,
-                                      int accumulate, hipStream_t st);
-hipError_t dtfk_colsum_bf16(const void* x, float* part, float* out, int N, int H, int P, int accumulate,
-                            hipStream_t st);
-hipError_t dtfk_slab_sum(const float* slabs, float* out, int S, long long n, int accumulate, hipStream_t st);
-hipError_t dtfk_bias_gelu_fwd(const void* x, const float* bias, void* y, long long n, int H, hipStream_t st);
-hipError_t dtfk_bias_gelu_bwd(const void* dy, const void* x, const float* bias, void* dx, float* part, int N, int H,
-                              int row_slices, hipStream_t st);
-hipError_t dtfk_softmax_fwd(const void* S, const float* mask, void* P, void* Pd, int rows, int Sk, int rows_per_batch,
-                            float scale, float p, unsigned long long seed, hipStream_t st);
-hipError_t dtfk_softmax_bwd(const void* dPd, const void* P, void* dS, int rows, int Sk, float scale, float p,
-                            unsigned long long seed, hipStream_t st);
-hipError_t dtfk_dropout_bf16(const void* x, void* y, long long n, float p, unsigned long long seed, hipStream_t st);
-int dtfk_attn_supported(int S, int d);
-hipError_t dtfk_attn_fwd(const void* qkv, const float* bias, const float* mask, void* ctx, float* lse, int B, int S,
-                         int NH, float scale, float p, unsigned long long seed, hipStream_t st);
-hipError_t dtfk_attn_bwd(const void* qkv, const float* bias, const float* mask, const void* ctx, const void* dctx,
-                         const float* lse, float* Dbuf, void* dqkv, int B, int S, int NH, float scale, float p,
-                         unsigned long long seed, float* bpart, hipStream_t st);
-}
+#include "bind_common.h"
+#include "kernels/transformer_api.h"
 
 namespace dtf {
 namespace {
-hipStream_t cs() { return c10::hip::getCurrentHIPStream().stream(); }
-void ck(hipError_t e, const char* w) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(w) + ": " + hipGetErrorString(e));
-}
-void req(const at::Tensor& t, at::ScalarType dt, const char* n) {
-  if (!t.is_cuda()) throw std::runtime_error(std::string(n) + " must be a GPU tensor");
-  if (t.scalar_type() != dt) throw std::runtime_error(std::string(n) + " has the wrong dtype");
-  if (!t.is_contiguous()) throw std::runtime_error(std::string(n) + " must be contiguous");
-}
-void* optp(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
-float* optf(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr<float>() : nullptr; }
 int rows_of(const at::Tensor& t, int H) { return (int)(t.numel() / H); }
-// size and range refusals, raised before any launch
-void need(bool ok, const char* what) {
-  if (!ok) throw std::runtime_error(what);
-}
 void need_p(double p, const char* op) {
-  need(p >= 0.0 && p < 1.0, (std::string(op) + ": dropout p must be in [0, 1)").c_str());
+  require(p >= 0.0 && p < 1.0, std::string(op) + ": dropout p must be in [0, 1)");
 }
 // the last dimension as the row width: at least 1, so that rows_of can divide by it
 int width_of(const at::Tensor& t, const char* op) {
-  need(t.dim() >= 1 && t.size(-1) > 0, (std::string(op) + ": the last dimension is empty").c_str());
+  require(t.dim() >= 1 && t.size(-1) > 0, std::string(op) + ": the last dimension is empty");
   return (int)t.size(-1);
 }
 }  // namespace
@@ -77,39 +20,40 @@ void bdrln_fwd(at::Tensor x, at::Tensor bias, c10::optional<at::Tensor> res, at:
                at::Tensor y, c10::optional<at::Tensor> s, at::Tensor mean, at::Tensor rstd, double eps, double p,
                int64_t seed) {
   const int H = width_of(x, "bdrln_fwd");
-  req(x, at::kBFloat16, "x"); req(y, at::kBFloat16, "y"); req(bias, at::kFloat, "bias");
-  req(gamma, at::kFloat, "gamma"); req(beta, at::kFloat, "beta"); req(mean, at::kFloat, "mean");
-  req(rstd, at::kFloat, "rstd");
-  if (res.has_value()) req(*res, at::kBFloat16, "res");
-  if (s.has_value()) req(*s, at::kBFloat16, "s");
+  need(x, at::kBFloat16, "x"); need(y, at::kBFloat16, "y"); need(bias, at::kFloat, "bias");
+  need(gamma, at::kFloat, "gamma"); need(beta, at::kFloat, "beta"); need(mean, at::kFloat, "mean");
+  need(rstd, at::kFloat, "rstd");
+  if (res.has_value()) need(*res, at::kBFloat16, "res");
+  if (s.has_value()) need(*s, at::kBFloat16, "s");
   const int N = rows_of(x, H);
   if (mean.numel() < N || rstd.numel() < N || y.numel() != x.numel()) throw std::runtime_error("bdrln_fwd shapes");
-  need(bias.numel() >= H && gamma.numel() >= H && beta.numel() >= H, "bdrln_fwd: bias / gamma / beta need H elements");
-  need(!res.has_value() || res->numel() == x.numel(), "bdrln_fwd: res size");
-  need(!s.has_value() || s->numel() == x.numel(), "bdrln_fwd: s size");
+  require(bias.numel() >= H && gamma.numel() >= H && beta.numel() >= H,
+          "bdrln_fwd: bias / gamma / beta need H elements");
+  require(!res.has_value() || res->numel() == x.numel(), "bdrln_fwd: res size");
+  require(!s.has_value() || s->numel() == x.numel(), "bdrln_fwd: s size");
   need_p(p, "bdrln_fwd");
-  ck(dtfk_bdrln_fwd(x.data_ptr(), bias.data_ptr<float>(), optp(res), gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                    y.data_ptr(), optp(s), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H, (float)eps,
-                    (float)p, (unsigned long long)seed, cs()),
-     "bdrln_fwd");
+  hip_check(dtfk_bdrln_fwd(x.data_ptr(), bias.data_ptr<float>(), opt_ptr(res), gamma.data_ptr<float>(),
+                           beta.data_ptr<float>(), y.data_ptr(), opt_ptr(s), mean.data_ptr<float>(),
+                           rstd.data_ptr<float>(), N, H, (float)eps, (float)p, (unsigned long long)seed, cur_stream()),
+            "bdrln_fwd");
 }
 
 void ln_fwd_f32in(at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor y, c10::optional<at::Tensor> s,
                   at::Tensor mean, at::Tensor rstd, double eps, double p, int64_t seed) {
   const int H = width_of(x, "ln_fwd_f32in");
-  req(x, at::kFloat, "x"); req(y, at::kBFloat16, "y");
-  req(gamma, at::kFloat, "gamma"); req(beta, at::kFloat, "beta"); req(mean, at::kFloat, "mean");
-  req(rstd, at::kFloat, "rstd");
-  if (s.has_value()) req(*s, at::kBFloat16, "s");
+  need(x, at::kFloat, "x"); need(y, at::kBFloat16, "y");
+  need(gamma, at::kFloat, "gamma"); need(beta, at::kFloat, "beta"); need(mean, at::kFloat, "mean");
+  need(rstd, at::kFloat, "rstd");
+  if (s.has_value()) need(*s, at::kBFloat16, "s");
   const int N = rows_of(x, H);
-  need(y.numel() == x.numel() && (!s.has_value() || s->numel() == x.numel()), "ln_fwd_f32in: y / s size");
-  need(gamma.numel() >= H && beta.numel() >= H, "ln_fwd_f32in: gamma / beta need H elements");
-  need(mean.numel() >= N && rstd.numel() >= N, "ln_fwd_f32in: mean / rstd need N elements");
+  require(y.numel() == x.numel() && (!s.has_value() || s->numel() == x.numel()), "ln_fwd_f32in: y / s size");
+  require(gamma.numel() >= H && beta.numel() >= H, "ln_fwd_f32in: gamma / beta need H elements");
+  require(mean.numel() >= N && rstd.numel() >= N, "ln_fwd_f32in: mean / rstd need N elements");
   need_p(p, "ln_fwd_f32in");
-  ck(dtfk_ln_fwd_f32in(x.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), y.data_ptr(), optp(s),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H, (float)eps, (float)p,
-                       (unsigned long long)seed, cs()),
-     "ln_fwd_f32in");
+  hip_check(dtfk_ln_fwd_f32in(x.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), y.data_ptr(),
+                              opt_ptr(s), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H, (float)eps, (float)p,
+                              (unsigned long long)seed, cur_stream()),
+            "ln_fwd_f32in");
 }
 
 // BERT embedding block: y = dropout(LN(word[ids] + typ[tt] + pos[t % S])), s = bf16 of the sum
@@ -117,39 +61,42 @@ void emb_ln_fwd(at::Tensor word, at::Tensor ids, at::Tensor typ, at::Tensor tt, 
                 at::Tensor gamma, at::Tensor beta, at::Tensor y, at::Tensor s, at::Tensor mean, at::Tensor rstd,
                 double eps, double p, int64_t seed) {
   const int H = (int)word.size(-1);
-  req(word, at::kFloat, "word"); req(typ, at::kFloat, "typ"); req(pos, at::kFloat, "pos");
-  req(gamma, at::kFloat, "gamma"); req(beta, at::kFloat, "beta");
-  req(y, at::kBFloat16, "y"); req(s, at::kBFloat16, "s"); req(mean, at::kFloat, "mean"); req(rstd, at::kFloat, "rstd");
-  req(ids, at::kLong, "ids"); req(tt, at::kLong, "tt");
+  need(word, at::kFloat, "word"); need(typ, at::kFloat, "typ"); need(pos, at::kFloat, "pos");
+  need(gamma, at::kFloat, "gamma"); need(beta, at::kFloat, "beta");
+  need(y, at::kBFloat16, "y"); need(s, at::kBFloat16, "s"); need(mean, at::kFloat, "mean");
+  need(rstd, at::kFloat, "rstd");
+  need(ids, at::kLong, "ids"); need(tt, at::kLong, "tt");
   const int64_t N = ids.numel();
   if (tt.numel() != N || y.numel() != N * H || s.numel() != N * H || mean.numel() < N || rstd.numel() < N ||
       typ.size(-1) != H || pos.size(-1) != H || pos.size(0) < S || S < 1 || N % S)
     throw std::runtime_error("emb_ln_fwd shapes");
-  need(N >= 1 && H >= 1 && gamma.numel() >= H && beta.numel() >= H, "emb_ln_fwd: gamma / beta need H elements");
+  require(N >= 1 && H >= 1 && gamma.numel() >= H && beta.numel() >= H, "emb_ln_fwd: gamma / beta need H elements");
   need_p(p, "emb_ln_fwd");
-  ck(dtfk_emb_ln_fwd(word.data_ptr<float>(), ids.data_ptr<int64_t>(), typ.data_ptr<float>(), tt.data_ptr<int64_t>(),
-                     pos.data_ptr<float>(), (int)S, gamma.data_ptr<float>(), beta.data_ptr<float>(), y.data_ptr(),
-                     s.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), (int)N, H, (float)eps, (float)p,
-                     (unsigned long long)seed, cs()),
-     "emb_ln_fwd");
+  hip_check(dtfk_emb_ln_fwd(word.data_ptr<float>(), ids.data_ptr<int64_t>(), typ.data_ptr<float>(),
+                            tt.data_ptr<int64_t>(), pos.data_ptr<float>(), (int)S, gamma.data_ptr<float>(),
+                            beta.data_ptr<float>(), y.data_ptr(), s.data_ptr(), mean.data_ptr<float>(),
+                            rstd.data_ptr<float>(), (int)N, H, (float)eps, (float)p, (unsigned long long)seed,
+                            cur_stream()),
+            "emb_ln_fwd");
 }
 // position / 2-row token-type gradients of the embedding block from ds [B*S, H] bf16:
 // pos_grad rows [0, S) (+)= sum over b; typ_grad [2, H] (+)= per-type sums
 void emb_bwd_aux(at::Tensor ds, at::Tensor tt, int64_t S, at::Tensor pos_grad, at::Tensor typ_grad, at::Tensor part,
                  bool accumulate) {
   const int H = (int)ds.size(-1);
-  req(ds, at::kBFloat16, "ds"); req(tt, at::kLong, "tt"); req(pos_grad, at::kFloat, "pos_grad");
-  req(typ_grad, at::kFloat, "typ_grad"); req(part, at::kFloat, "part");
+  need(ds, at::kBFloat16, "ds"); need(tt, at::kLong, "tt"); need(pos_grad, at::kFloat, "pos_grad");
+  need(typ_grad, at::kFloat, "typ_grad"); need(part, at::kFloat, "part");
   const int64_t N = tt.numel();
   if (S < 1 || N % S || ds.numel() != N * H || pos_grad.numel() < S * H || typ_grad.numel() < 2 * H ||
       part.numel() < 2 * S * H)
     throw std::runtime_error("emb_bwd_aux shapes");
-  ck(dtfk_emb_bwd_aux(ds.data_ptr(), tt.data_ptr<int64_t>(), (int)(N / S), (int)S, H, pos_grad.data_ptr<float>(),
-                      part.data_ptr<float>(), accumulate ? 1 : 0, cs()),
-     "emb_bwd_aux");
+  hip_check(dtfk_emb_bwd_aux(ds.data_ptr(), tt.data_ptr<int64_t>(), (int)(N / S), (int)S, H, pos_grad.data_ptr<float>(),
+                             part.data_ptr<float>(), accumulate ? 1 : 0, cur_stream()),
+            "emb_bwd_aux");
   const float* parts[2] = {part.data_ptr<float>(), part.data_ptr<float>() + S * H};
   float* outs[2] = {typ_grad.data_ptr<float>(), typ_grad.data_ptr<float>() + H};
-  ck(dtfk_colsum_partials_multi(parts, outs, 2, (int)S, H, accumulate ? 1 : 0, cs()), "emb_bwd_aux colsum");
+  hip_check(dtfk_colsum_partials_multi(parts, outs, 2, (int)S, H, accumulate ? 1 : 0, cur_stream()),
+            "emb_bwd_aux colsum");
 }
 
 // returns nothing; dgamma/dbeta/dbias (fp32 [H]) written if given
@@ -158,37 +105,38 @@ void ln_bwd(at::Tensor dy, at::Tensor s, at::Tensor mean, at::Tensor rstd, at::T
             c10::optional<at::Tensor> dbeta, c10::optional<at::Tensor> dbias, double p, int64_t seed,
             bool accumulate) {
   const int H = width_of(dy, "ln_bwd");
-  req(dy, at::kBFloat16, "dy"); req(s, at::kBFloat16, "s"); req(ds, at::kBFloat16, "ds");
-  req(part, at::kFloat, "part"); req(mean, at::kFloat, "mean"); req(rstd, at::kFloat, "rstd");
-  req(gamma, at::kFloat, "gamma");
-  if (dxb.has_value()) req(*dxb, at::kBFloat16, "dxb");
+  need(dy, at::kBFloat16, "dy"); need(s, at::kBFloat16, "s"); need(ds, at::kBFloat16, "ds");
+  need(part, at::kFloat, "part"); need(mean, at::kFloat, "mean"); need(rstd, at::kFloat, "rstd");
+  need(gamma, at::kFloat, "gamma");
+  if (dxb.has_value()) need(*dxb, at::kBFloat16, "dxb");
   const int N = rows_of(dy, H);
   const int grid = (int)(part.numel() / (3LL * H));
   if (grid < 1) throw std::runtime_error("ln_bwd: partial buffer too small (needs 3*grid*H floats)");
-  need(s.numel() == dy.numel() && ds.numel() == dy.numel() && (!dxb.has_value() || dxb->numel() == dy.numel()),
-       "ln_bwd: s / ds / dxb size");
-  need(mean.numel() >= N && rstd.numel() >= N, "ln_bwd: mean / rstd need N elements");
-  need(gamma.numel() >= H, "ln_bwd: gamma needs H elements");
+  require(s.numel() == dy.numel() && ds.numel() == dy.numel() && (!dxb.has_value() || dxb->numel() == dy.numel()),
+          "ln_bwd: s / ds / dxb size");
+  require(mean.numel() >= N && rstd.numel() >= N, "ln_bwd: mean / rstd need N elements");
+  require(gamma.numel() >= H, "ln_bwd: gamma needs H elements");
   need_p(p, "ln_bwd");
   for (const auto* t : {&dgamma, &dbeta, &dbias})
     if (t->has_value()) {
-      req(**t, at::kFloat, "param grad");
-      need((*t)->numel() >= H, "ln_bwd: gradient output too small");
+      need(**t, at::kFloat, "param grad");
+      require((*t)->numel() >= H, "ln_bwd: gradient output too small");
     }
   float* pg = part.data_ptr<float>();
   float* pb = pg + (size_t)grid * H;
   float* px = pb + (size_t)grid * H;
-  ck(dtfk_ln_bwd(dy.data_ptr(), s.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                 ds.data_ptr(), optp(dxb), dgamma.has_value() ? pg : nullptr, dbeta.has_value() ? pb : nullptr,
-                 dbias.has_value() ? px : nullptr, grid, N, H, (float)p, (unsigned long long)seed, cs()),
-     "ln_bwd");
+  hip_check(dtfk_ln_bwd(dy.data_ptr(), s.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                        gamma.data_ptr<float>(), ds.data_ptr(), opt_ptr(dxb), dgamma.has_value() ? pg : nullptr,
+                        dbeta.has_value() ? pb : nullptr, dbias.has_value() ? px : nullptr, grid, N, H, (float)p,
+                        (unsigned long long)seed, cur_stream()),
+            "ln_bwd");
   // dgamma / dbeta / dbias: one finishing launch (accumulate: += into sunk .grad)
   const float* parts[3];
   float* outs[3];
   int nb = 0;
   auto add = [&](const c10::optional<at::Tensor>& t, const float* pp) {
     if (!t.has_value()) return;
-    req(*t, at::kFloat, "param grad");
+    need(*t, at::kFloat, "param grad");
     if (t->numel() < H) throw std::runtime_error("ln_bwd: gradient output too small");
     parts[nb] = pp;
     outs[nb++] = t->data_ptr<float>();
@@ -196,105 +144,109 @@ void ln_bwd(at::Tensor dy, at::Tensor s, at::Tensor mean, at::Tensor rstd, at::T
   add(dgamma, pg);
   add(dbeta, pb);
   add(dbias, px);
-  if (nb) ck(dtfk_colsum_partials_multi(parts, outs, nb, grid, H, accumulate ? 1 : 0, cs()), "colsum");
+  if (nb) hip_check(dtfk_colsum_partials_multi(parts, outs, nb, grid, H, accumulate ? 1 : 0, cur_stream()), "colsum");
 }
 
 // bias gradient of a bf16 [N, H] matrix: out (+)= column sums (part: P*H floats)
 void colsum_bf16(at::Tensor x, at::Tensor part, at::Tensor out, bool accumulate) {
-  req(x, at::kBFloat16, "x"); req(part, at::kFloat, "part"); req(out, at::kFloat, "out");
+  need(x, at::kBFloat16, "x"); need(part, at::kFloat, "part"); need(out, at::kFloat, "out");
   const int H = width_of(x, "colsum_bf16");
   const int N = rows_of(x, H);
   const int P = (int)(part.numel() / H);
   if (P < 1 || out.numel() < H) throw std::runtime_error("colsum_bf16 shapes");
-  ck(dtfk_colsum_bf16(x.data_ptr(), part.data_ptr<float>(), out.data_ptr<float>(), N, H, P, accumulate ? 1 : 0, cs()),
-     "colsum_bf16");
+  hip_check(dtfk_colsum_bf16(x.data_ptr(), part.data_ptr<float>(), out.data_ptr<float>(), N, H, P, accumulate ? 1 : 0,
+                             cur_stream()),
+            "colsum_bf16");
 }
 
 // out (+)= sum over the leading dim of slabs [S, n] (fp32; 16-byte vector path when aligned)
 void slab_sum(at::Tensor slabs, at::Tensor out, bool accumulate) {
-  req(slabs, at::kFloat, "slabs"); req(out, at::kFloat, "out");
+  need(slabs, at::kFloat, "slabs"); need(out, at::kFloat, "out");
   const int64_t n = out.numel();
   if (n == 0 || slabs.numel() % n) throw std::runtime_error("slab_sum shapes");
   if (!slabs.is_contiguous() || !out.is_contiguous()) throw std::runtime_error("slab_sum: contiguous tensors only");
   const int S = (int)(slabs.numel() / n);
-  ck(dtfk_slab_sum(slabs.data_ptr<float>(), out.data_ptr<float>(), S, n, accumulate ? 1 : 0, cs()), "slab_sum");
+  hip_check(dtfk_slab_sum(slabs.data_ptr<float>(), out.data_ptr<float>(), S, n, accumulate ? 1 : 0, cur_stream()),
+            "slab_sum");
 }
 
 void bias_gelu_fwd(at::Tensor x, at::Tensor bias, at::Tensor y) {
-  req(x, at::kBFloat16, "x"); req(y, at::kBFloat16, "y"); req(bias, at::kFloat, "bias");
+  need(x, at::kBFloat16, "x"); need(y, at::kBFloat16, "y"); need(bias, at::kFloat, "bias");
   const int H = width_of(x, "bias_gelu_fwd");
   if (H % 4) throw std::runtime_error("bias_gelu: H % 4 != 0");
-  need(bias.numel() >= H && y.numel() == x.numel(), "bias_gelu_fwd: bias needs H elements, y the size of x");
-  ck(dtfk_bias_gelu_fwd(x.data_ptr(), bias.data_ptr<float>(), y.data_ptr(), x.numel(), H, cs()), "bias_gelu_fwd");
+  require(bias.numel() >= H && y.numel() == x.numel(), "bias_gelu_fwd: bias needs H elements, y the size of x");
+  hip_check(dtfk_bias_gelu_fwd(x.data_ptr(), bias.data_ptr<float>(), y.data_ptr(), x.numel(), H, cur_stream()),
+            "bias_gelu_fwd");
 }
 
 void bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias, at::Tensor dx, at::Tensor part, at::Tensor dbias,
                    bool accumulate) {
-  req(dy, at::kBFloat16, "dy"); req(x, at::kBFloat16, "x"); req(dx, at::kBFloat16, "dx");
-  req(part, at::kFloat, "part"); req(dbias, at::kFloat, "dbias");
+  need(dy, at::kBFloat16, "dy"); need(x, at::kBFloat16, "x"); need(dx, at::kBFloat16, "dx");
+  need(part, at::kFloat, "part"); need(dbias, at::kFloat, "dbias");
   const int H = width_of(x, "bias_gelu_bwd");
   const int N = rows_of(x, H);
   const int slices = (int)(part.numel() / H);
   if (slices < 1 || H % 4) throw std::runtime_error("bias_gelu_bwd shapes");
-  need(bias.numel() >= H && dbias.numel() >= H && dy.numel() == x.numel() && dx.numel() == x.numel(),
-       "bias_gelu_bwd: bias / dbias need H elements, dy / dx the size of x");
-  ck(dtfk_bias_gelu_bwd(dy.data_ptr(), x.data_ptr(), bias.data_ptr<float>(), dx.data_ptr(), part.data_ptr<float>(), N,
-                        H, slices, cs()),
-     "bias_gelu_bwd");
+  require(bias.numel() >= H && dbias.numel() >= H && dy.numel() == x.numel() && dx.numel() == x.numel(),
+          "bias_gelu_bwd: bias / dbias need H elements, dy / dx the size of x");
+  hip_check(dtfk_bias_gelu_bwd(dy.data_ptr(), x.data_ptr(), bias.data_ptr<float>(), dx.data_ptr(),
+                               part.data_ptr<float>(), N, H, slices, cur_stream()),
+            "bias_gelu_bwd");
   const float* pp[1] = {part.data_ptr<float>()};
   float* po[1] = {dbias.data_ptr<float>()};
-  ck(dtfk_colsum_partials_multi(pp, po, 1, slices, H, accumulate ? 1 : 0, cs()), "colsum");
+  hip_check(dtfk_colsum_partials_multi(pp, po, 1, slices, H, accumulate ? 1 : 0, cur_stream()), "colsum");
 }
 
 void softmax_fwd(at::Tensor S, c10::optional<at::Tensor> mask, at::Tensor P, c10::optional<at::Tensor> Pd,
                  int64_t rows_per_batch, double scale, double p, int64_t seed) {
-  req(S, at::kBFloat16, "S"); req(P, at::kBFloat16, "P");
-  if (Pd.has_value()) req(*Pd, at::kBFloat16, "Pd");
-  if (mask.has_value()) req(*mask, at::kFloat, "mask");
+  need(S, at::kBFloat16, "S"); need(P, at::kBFloat16, "P");
+  if (Pd.has_value()) need(*Pd, at::kBFloat16, "Pd");
+  if (mask.has_value()) need(*mask, at::kFloat, "mask");
   const int Sk = width_of(S, "softmax_fwd");
   const int rows = (int)(S.numel() / Sk);
-  need(rows_per_batch >= 1, "softmax_fwd: rows_per_batch must be at least 1");
-  need(P.numel() == S.numel() && (!Pd.has_value() || Pd->numel() == S.numel()), "softmax_fwd: P / Pd size");
-  need(!mask.has_value() || mask->numel() >= ((int64_t)rows + rows_per_batch - 1) / rows_per_batch * Sk,
-       "softmax_fwd: mask needs ceil(rows / rows_per_batch) * Sk elements");
+  require(rows_per_batch >= 1, "softmax_fwd: rows_per_batch must be at least 1");
+  require(P.numel() == S.numel() && (!Pd.has_value() || Pd->numel() == S.numel()), "softmax_fwd: P / Pd size");
+  require(!mask.has_value() || mask->numel() >= ((int64_t)rows + rows_per_batch - 1) / rows_per_batch * Sk,
+          "softmax_fwd: mask needs ceil(rows / rows_per_batch) * Sk elements");
   need_p(p, "softmax_fwd");
-  ck(dtfk_softmax_fwd(S.data_ptr(), optf(mask), P.data_ptr(), optp(Pd), rows, Sk, (int)rows_per_batch, (float)scale,
-                      (float)p, (unsigned long long)seed, cs()),
-     "softmax_fwd");
+  hip_check(dtfk_softmax_fwd(S.data_ptr(), opt_ptr<float>(mask), P.data_ptr(), opt_ptr(Pd), rows, Sk,
+                             (int)rows_per_batch, (float)scale, (float)p, (unsigned long long)seed, cur_stream()),
+            "softmax_fwd");
 }
 
 void softmax_bwd(at::Tensor dPd, at::Tensor P, at::Tensor dS, double scale, double p, int64_t seed) {
-  req(dPd, at::kBFloat16, "dPd"); req(P, at::kBFloat16, "P"); req(dS, at::kBFloat16, "dS");
+  need(dPd, at::kBFloat16, "dPd"); need(P, at::kBFloat16, "P"); need(dS, at::kBFloat16, "dS");
   const int Sk = width_of(P, "softmax_bwd");
   const int rows = (int)(P.numel() / Sk);
-  need(dPd.numel() == P.numel() && dS.numel() == P.numel(), "softmax_bwd: dPd / dS size");
+  require(dPd.numel() == P.numel() && dS.numel() == P.numel(), "softmax_bwd: dPd / dS size");
   need_p(p, "softmax_bwd");
-  ck(dtfk_softmax_bwd(dPd.data_ptr(), P.data_ptr(), dS.data_ptr(), rows, Sk, (float)scale, (float)p,
-                      (unsigned long long)seed, cs()),
-     "softmax_bwd");
+  hip_check(dtfk_softmax_bwd(dPd.data_ptr(), P.data_ptr(), dS.data_ptr(), rows, Sk, (float)scale, (float)p,
+                             (unsigned long long)seed, cur_stream()),
+            "softmax_bwd");
 }
 
 void dropout_bf16(at::Tensor x, at::Tensor y, double p, int64_t seed) {
-  req(x, at::kBFloat16, "x"); req(y, at::kBFloat16, "y");
+  need(x, at::kBFloat16, "x"); need(y, at::kBFloat16, "y");
   if (x.numel() % 4) throw std::runtime_error("dropout_bf16: numel % 4 != 0");
-  need(y.numel() == x.numel(), "dropout_bf16: y size");
+  require(y.numel() == x.numel(), "dropout_bf16: y size");
   need_p(p, "dropout_bf16");
-  ck(dtfk_dropout_bf16(x.data_ptr(), y.data_ptr(), x.numel(), (float)p, (unsigned long long)seed, cs()), "dropout");
+  hip_check(dtfk_dropout_bf16(x.data_ptr(), y.data_ptr(), x.numel(), (float)p, (unsigned long long)seed, cur_stream()),
+            "dropout");
 }
 
 // qkv [B, S, 3*NH*64] bf16 (pre-bias projection), bias [3*NH*64] fp32 or None,
 // mask [B, S] additive fp32 or None -> ctx [B, S, NH*64] bf16, lse [B, NH, S] fp32
 void attn_check(const at::Tensor& qkv, const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& mask,
                 int64_t NH) {
-  req(qkv, at::kBFloat16, "qkv");
+  need(qkv, at::kBFloat16, "qkv");
   if (qkv.dim() != 3 || qkv.size(2) != 3 * NH * 64) throw std::runtime_error("attn: qkv must be [B, S, 3*NH*64]");
   if (!dtfk_attn_supported((int)qkv.size(1), 64)) throw std::runtime_error("attn: unsupported sequence length");
   if (bias.has_value()) {
-    req(*bias, at::kFloat, "bias");
+    need(*bias, at::kFloat, "bias");
     if (bias->numel() != qkv.size(2)) throw std::runtime_error("attn: bias size");
   }
   if (mask.has_value()) {
-    req(*mask, at::kFloat, "mask");
+    need(*mask, at::kFloat, "mask");
     if (mask->numel() != qkv.size(0) * qkv.size(1)) throw std::runtime_error("attn: mask must be [B, S]");
   }
 }
@@ -303,11 +255,12 @@ void attn_fwd(at::Tensor qkv, c10::optional<at::Tensor> bias, c10::optional<at::
               at::Tensor lse, int64_t NH, double scale, double p, int64_t seed) {
   attn_check(qkv, bias, mask, NH);
   const int64_t B = qkv.size(0), S = qkv.size(1);
-  req(ctx, at::kBFloat16, "ctx"); req(lse, at::kFloat, "lse");
+  need(ctx, at::kBFloat16, "ctx"); need(lse, at::kFloat, "lse");
   if (ctx.numel() != B * S * NH * 64 || lse.numel() != B * NH * S) throw std::runtime_error("attn_fwd: output sizes");
-  ck(dtfk_attn_fwd(qkv.data_ptr(), optf(bias), optf(mask), ctx.data_ptr(), lse.data_ptr<float>(), (int)B, (int)S,
-                   (int)NH, (float)scale, (float)p, (unsigned long long)seed, cs()),
-     "attn_fwd");
+  hip_check(dtfk_attn_fwd(qkv.data_ptr(), opt_ptr<float>(bias), opt_ptr<float>(mask), ctx.data_ptr(),
+                          lse.data_ptr<float>(), (int)B, (int)S, (int)NH, (float)scale, (float)p,
+                          (unsigned long long)seed, cur_stream()),
+            "attn_fwd");
 }
 
 // dbias (optional, with bpart [B * S / 16, 3 * NH * 64] fp32 scratch): the qkv
@@ -318,26 +271,28 @@ void attn_bwd(at::Tensor qkv, c10::optional<at::Tensor> bias, c10::optional<at::
               int64_t seed, c10::optional<at::Tensor> bpart, c10::optional<at::Tensor> dbias, bool accumulate) {
   attn_check(qkv, bias, mask, NH);
   const int64_t B = qkv.size(0), S = qkv.size(1);
-  req(ctx, at::kBFloat16, "ctx"); req(dctx, at::kBFloat16, "dctx"); req(dqkv, at::kBFloat16, "dqkv");
-  req(lse, at::kFloat, "lse"); req(Dbuf, at::kFloat, "Dbuf");
+  need(ctx, at::kBFloat16, "ctx"); need(dctx, at::kBFloat16, "dctx"); need(dqkv, at::kBFloat16, "dqkv");
+  need(lse, at::kFloat, "lse"); need(Dbuf, at::kFloat, "Dbuf");
   if (ctx.numel() != B * S * NH * 64 || dctx.numel() != ctx.numel() || dqkv.numel() != qkv.numel() ||
       lse.numel() != B * NH * S || Dbuf.numel() != lse.numel())
     throw std::runtime_error("attn_bwd: sizes");
   const int64_t H3 = 3 * NH * 64, P = B * S / 16;
   if (bpart.has_value() != dbias.has_value()) throw std::runtime_error("attn_bwd: bpart and dbias go together");
   if (bpart.has_value()) {
-    req(*bpart, at::kFloat, "bpart"); req(*dbias, at::kFloat, "dbias");
+    need(*bpart, at::kFloat, "bpart"); need(*dbias, at::kFloat, "dbias");
     if (bpart->numel() < P * H3 || dbias->numel() != H3 || !dbias->is_contiguous())
       throw std::runtime_error("attn_bwd: bpart needs B*S/16 x 3*NH*64 floats, dbias 3*NH*64");
   }
-  ck(dtfk_attn_bwd(qkv.data_ptr(), optf(bias), optf(mask), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
-                   Dbuf.data_ptr<float>(), dqkv.data_ptr(), (int)B, (int)S, (int)NH, (float)scale, (float)p,
-                   (unsigned long long)seed, bpart.has_value() ? bpart->data_ptr<float>() : nullptr, cs()),
-     "attn_bwd");
+  hip_check(dtfk_attn_bwd(qkv.data_ptr(), opt_ptr<float>(bias), opt_ptr<float>(mask), ctx.data_ptr(), dctx.data_ptr(),
+                          lse.data_ptr<float>(), Dbuf.data_ptr<float>(), dqkv.data_ptr(), (int)B, (int)S, (int)NH,
+                          (float)scale, (float)p, (unsigned long long)seed,
+                          bpart.has_value() ? bpart->data_ptr<float>() : nullptr, cur_stream()),
+            "attn_bwd");
   if (bpart.has_value()) {
     const float* pp[1] = {bpart->data_ptr<float>()};
     float* po[1] = {dbias->data_ptr<float>()};
-    ck(dtfk_colsum_partials_multi(pp, po, 1, (int)P, (int)H3, accumulate ? 1 : 0, cs()), "attn_bwd dbias");
+    hip_check(dtfk_colsum_partials_multi(pp, po, 1, (int)P, (int)H3, accumulate ? 1 : 0, cur_stream()),
+              "attn_bwd dbias");
   }
 }
 

@@ -5,10 +5,7 @@
 // checks everything first and then makes its two launches on the current
 // stream: no host read-back, no memset node, so it can be captured in a
 // hipGraph (the capture holds the tensors' and the scratch's addresses).
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
-
+#include "bind_common.h"
 #include "eval_record_host.h"
 #include "kernels/wide_deep_eval.h"
 
@@ -106,10 +103,10 @@ class WideDeepEvalPlan {
     a.brow = reinterpret_cast<int*>(scratch_.part(2));
     a.p_out = o.pred;
     a.z_out = o.logits;
-    hipStream_t st = c10::hip::getCurrentHIPStream().stream();
-    hck_(dtfk_wd_eval_rows(&a, tile_, st), "WideDeepEvalPlan: rows kernel");
-    hck_(dtfk_eval_reduce(a.lrow, a.prow, a.brow, a.labels, a.B, o.T, o.reset, o.rec, st),
-         "WideDeepEvalPlan: reduce kernel");
+    hipStream_t st = cur_stream();
+    hip_check(dtfk_wd_eval_rows(&a, tile_, st), "WideDeepEvalPlan: rows kernel");
+    hip_check(dtfk_eval_reduce(a.lrow, a.prow, a.brow, a.labels, a.B, o.T, o.reset, o.rec, st),
+              "WideDeepEvalPlan: reduce kernel");
     ++eval_runs_;
   }
 
@@ -124,9 +121,6 @@ class WideDeepEvalPlan {
   at::Tensor scratch() const { return scratch_.tensor(); }   // thirds: lrow | prow | bad ids per row (int)
 
  private:
-  static void hck_(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-  }
   at::Tensor wide_, emb_, bias_;
   std::vector<at::Tensor> layers_;
   EvalScratch scratch_{3};

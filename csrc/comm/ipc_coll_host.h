@@ -16,9 +16,7 @@
 // * Errors (a bounded wait timed out, a peer's overflow) land in a pinned host
 //   word the kernels write; every call checks it first and raises.
 #pragma once
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
+#include "bind_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -46,7 +44,7 @@ class IpcColl {
     timeout_ = (long long)(std::max(0.001, timeout_s) * 1e8);   // s_memrealtime: 100 MHz
     const char* nw = std::getenv("DTF_IPC_NARROW");                // A/B probe: 8-byte peer loads
     wide_ = (nw != nullptr && nw[0] == '1') ? 0 : 1;
-    ck(hipEventCreateWithFlags(&ev_, hipEventDisableTiming), "hipEventCreate");
+    hip_check(hipEventCreateWithFlags(&ev_, hipEventDisableTiming), "hipEventCreate");
   }
   ~IpcColl() {
     if (ev_) (void)hipEventDestroy(ev_);
@@ -82,10 +80,10 @@ class IpcColl {
   // -------------------------------------------------------------- stream order
   hipStream_t begin() {
     check();
-    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    hipStream_t s = cur_stream();
     if (last_ != nullptr && last_ != s) {       // chain: everything queued on the old stream first
-      ck(hipEventRecord(ev_, last_), "IpcColl: event");
-      ck(hipStreamWaitEvent(s, ev_, 0), "IpcColl: wait");
+      hip_check(hipEventRecord(ev_, last_), "IpcColl: event");
+      hip_check(hipStreamWaitEvent(s, ev_, 0), "IpcColl: wait");
     }
     last_ = s;
     ++calls_;
@@ -110,9 +108,9 @@ class IpcColl {
     for (int64_t off = 0; off < n; off += chunk) {
       const int64_t m = std::min(chunk, n - off);
       const int two = (W_ > 2 && m * es >= two_shot_) ? 1 : 0;
-      ck(dtfk_ipcc_allreduce(static_cast<const char*>(in) + off * es, static_cast<char*>(out) + off * es, m, dtype,
-                             op, scale, two, coll(), grid_for(m * es), s),
-         "IpcColl: all_reduce launch");
+      hip_check(dtfk_ipcc_allreduce(static_cast<const char*>(in) + off * es, static_cast<char*>(out) + off * es, m,
+                                    dtype, op, scale, two, coll(), grid_for(m * es), s),
+                "IpcColl: all_reduce launch");
     }
   }
 
@@ -141,7 +139,7 @@ class IpcColl {
     a.gkind = gkind;
     a.metrics = metrics;
     a.host_metrics = host_metrics;
-    ck(dtfk_ipcc_reduce_sgd(grad, n, a, coll(), grid_for(n * 4), s), "IpcColl: reduce_sgd launch");
+    hip_check(dtfk_ipcc_reduce_sgd(grad, n, a, coll(), grid_for(n * 4), s), "IpcColl: reduce_sgd launch");
   }
 
   void broadcast_raw(void* buf, int64_t nbytes, int src, hipStream_t s) {
@@ -151,7 +149,7 @@ class IpcColl {
     for (int64_t off = 0; off < nbytes; off += chunk) {
       const int64_t m = std::min(chunk, nbytes - off);
       char* p = static_cast<char*>(buf) + off;
-      ck(dtfk_ipcc_broadcast(p, p, m, src, coll(), grid_for(m), s), "IpcColl: broadcast launch");
+      hip_check(dtfk_ipcc_broadcast(p, p, m, src, coll(), grid_for(m), s), "IpcColl: broadcast launch");
     }
   }
 
@@ -161,9 +159,9 @@ class IpcColl {
     const int64_t chunk = cap_ / 16 * 16;
     for (int64_t off = 0; off < nbytes; off += chunk) {
       const int64_t m = std::min(chunk, nbytes - off);
-      ck(dtfk_ipcc_allgather(static_cast<const char*>(in) + off, static_cast<char*>(out) + off, m, nbytes, coll(),
-                             grid_for(m * W_), s),
-         "IpcColl: all_gather launch");
+      hip_check(dtfk_ipcc_allgather(static_cast<const char*>(in) + off, static_cast<char*>(out) + off, m, nbytes,
+                                    coll(), grid_for(m * W_), s),
+                "IpcColl: all_gather launch");
     }
   }
 
@@ -187,7 +185,7 @@ class IpcColl {
       throw std::runtime_error("IpcColl.all_to_all: 4-byte aligned buffers expected");
     a.send_total = so;
     a.overflow = so > cap_ ? 1 : 0;
-    ck(dtfk_ipcc_alltoall(in, out, a, coll(), grid_for(std::max(so, ro)), s), "IpcColl: all_to_all launch");
+    hip_check(dtfk_ipcc_alltoall(in, out, a, coll(), grid_for(std::max(so, ro)), s), "IpcColl: all_to_all launch");
     if (a.overflow)
       throw std::runtime_error("IpcColl.all_to_all: this rank's send buffer (" + std::to_string(so) +
                                " bytes) exceeds the IPC slot capacity (" + std::to_string(cap_) +
@@ -195,10 +193,6 @@ class IpcColl {
   }
 
  private:
-  static void ck(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-  }
-
   py::object keep_;                 // the IpcPeerBuffers whose memory the table points into
   void* const* table_ = nullptr;
   int W_, rank_;

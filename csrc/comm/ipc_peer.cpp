@@ -11,36 +11,28 @@
 // Layout of a rank's buffer is decided by the user (the MLP uses
 // [flags 256 B][grad parity 0][grad parity 1]); tensor(offset, numel, dtype)
 // exposes a region of the OWN buffer as a non-owning torch tensor.
-#include <torch/extension.h>
-#include <hip/hip_runtime.h>
+#include "bind_common.h"
 
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 namespace dtf {
-namespace {
-void hck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-}  // namespace
 
 class IpcPeerBuffers {
  public:
   IpcPeerBuffers(int64_t nbytes, int world_size, int rank)
       : nbytes_(nbytes), world_(world_size), rank_(rank), peers_(world_size, nullptr) {
     if (world_size < 1 || rank < 0 || rank >= world_size) throw std::runtime_error("bad world/rank");
-    hck(hipGetDevice(&device_), "hipGetDevice");
-    hck(hipExtMallocWithFlags(&own_, (size_t)nbytes, hipDeviceMallocUncached), "hipExtMallocWithFlags(uncached)");
-    hck(hipMemset(own_, 0, (size_t)nbytes), "hipMemset");
+    hip_check(hipGetDevice(&device_), "hipGetDevice");
+    hip_check(hipExtMallocWithFlags(&own_, (size_t)nbytes, hipDeviceMallocUncached), "hipExtMallocWithFlags(uncached)");
+    hip_check(hipMemset(own_, 0, (size_t)nbytes), "hipMemset");
     peers_[rank] = own_;
-    hck(hipMalloc(&table_, sizeof(void*) * world_size), "hipMalloc(table)");
+    hip_check(hipMalloc(&table_, sizeof(void*) * world_size), "hipMalloc(table)");
   }
   ~IpcPeerBuffers() { close(); }
 
   py::bytes handle() const {
     hipIpcMemHandle_t h;
-    hck(hipIpcGetMemHandle(&h, own_), "hipIpcGetMemHandle");
+    hip_check(hipIpcGetMemHandle(&h, own_), "hipIpcGetMemHandle");
     return py::bytes(reinterpret_cast<const char*>(&h), sizeof(h));
   }
 
@@ -53,11 +45,11 @@ class IpcPeerBuffers {
       hipIpcMemHandle_t h;
       memcpy(&h, handles[r].data(), sizeof(h));
       void* p = nullptr;
-      hck(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
+      hip_check(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
       peers_[r] = p;
       opened_.push_back(p);
     }
-    hck(hipMemcpy(table_, peers_.data(), sizeof(void*) * world_, hipMemcpyHostToDevice), "hipMemcpy(table)");
+    hip_check(hipMemcpy(table_, peers_.data(), sizeof(void*) * world_, hipMemcpyHostToDevice), "hipMemcpy(table)");
     ready_ = true;
   }
 

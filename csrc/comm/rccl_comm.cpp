@@ -6,8 +6,8 @@
 // captured into a hipGraph together with the compute kernels of a step.
 // Bootstrap (unique-id exchange) is done by the Python control plane over
 // the TCP store; this file only owns the communicator.
-#include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
+#include "bind_common.h"
+
 #include <rccl/rccl.h>
 
 #include <chrono>
@@ -59,8 +59,6 @@ static ncclRedOp_t to_op(const std::string& op) {
   if (op == "avg") return ncclAvg;
   throw std::runtime_error("unknown reduce op " + op);
 }
-
-static hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 py::bytes rccl_unique_id() {
   ncclUniqueId id;

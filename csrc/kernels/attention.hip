@@ -32,6 +32,7 @@
 // the [B, NH, S, S] probability tensor -- the same convention as the unfused
 // softmax kernel (transformer.hip), so both paths drop the same elements.
 #include "common.h"
+#include "transformer_api.h"
 
 #include <cstdlib>
 #include <string>

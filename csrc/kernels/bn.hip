@@ -16,6 +16,7 @@
 // Layout: x is [M, C] with M = N*H*W rows, 8 channels per thread (16-byte
 // bf16x8 accesses), C % 8 == 0.  Partial buffers are [P, C] fp32 and are
 // reduced in a fixed order (deterministic).
+#include "bn_api.h"
 #include "common.h"
 #include <cstdlib>
 

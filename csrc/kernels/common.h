@@ -13,6 +13,14 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+// native integer vectors for register staging (an array of HIP's struct uint4 stayed in scratch memory)
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(4))) short v4s;
+// pointees in the LDS / global address spaces: what the transposed LDS read and global_load_lds take
+typedef __attribute__((address_space(3))) v4s lds_v4s;
+typedef __attribute__((address_space(3))) void lvoid;
+typedef __attribute__((address_space(1))) void gvoid;
 
 constexpr int kWave = 64;
 
@@ -21,6 +29,12 @@ constexpr int kWave = 64;
 // C/D[4*(l>>4)+i][l&15] (i = 0..3).
 __device__ __forceinline__ f32x4 mfma16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+// D = A(16x4) * B(4x16) + C with fp32 operands (v_mfma_f32_16x16x4_f32): lane l holds A[l&15][l>>4],
+// B[l>>4][l&15] and C/D as mfma16x16x32.
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
 // D = A(32x16) * B(16x32) + C. Lane l holds A[l&31][8*(l>>5)+j],

@@ -55,14 +55,14 @@
 // weight gradient (conv_wgrad) is split over pixels into fp32 slabs summed in
 // split order by wgrad_reduce (profiles/conv_wgrad_sweep_r5.txt).
 #include "common.h"
+#include "conv_igemm_api.h"
+#include "lds_tr.h"
 #include <cstdlib>
 
 #include <type_traits>
 
 namespace dtfk {
 namespace cig {
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 constexpr int BM = 128, BK = 64, NTHR = 256;
 constexpr int OOB = 0x7ffffff0;
@@ -467,32 +467,7 @@ __global__ __launch_bounds__(NTHR, ONE ? 3 : 2) void conv_fwd(const uint16_t* __
 // fragments are read with the gfx950 transposed LDS read ds_read_b64_tr_b16
 // (4 x 16-bit down a column per lane, two per 8-deep fragment).  Pixel rows
 // advance 64 per step by a carried (n, ho, wo) counter, no divisions in the loop.
-// chunk XOR of pixel row k (as gemm_big.hip mn_sw: R = 64 rows are 128 B, two
-// per bank row, so k bit 0 picks the half and the XOR takes bits 1 and 3)
-__device__ __forceinline__ int mn_swz(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-template <int R>
-__device__ __forceinline__ int mn_sw(int k) {
-  if constexpr (R == 64) return (((k >> 1) & 1) | (((k >> 3) & 1) << 1)) << 1;
-  else return (mn_swz(k) << 1) & (R / 8 - 1);
-}
-template <int R>
-__device__ __forceinline__ int mn_off(int k, int ch) {   // byte offset of (k, 16-byte chunk ch) in [64][R]
-  return k * (2 * R) + ((ch ^ mn_sw<R>(k)) << 4);
-}
-typedef __attribute__((ext_vector_type(4))) short v4s;
-typedef __attribute__((address_space(3))) v4s lds_v4s;
-// MFMA 16x16x32 fragment of rows [rb, rb+16), k-sub s of a [64][R] image
-template <int R>
-__device__ __forceinline__ bf16x8 frag_tr(const uint8_t* img, int rb, int s, int lane) {
-  const int k = s * 32 + 8 * (lane >> 4) + ((lane & 15) >> 2);
-  const int mn = rb + 4 * (lane & 3);
-  const int off = mn_off<R>(k, mn >> 3) + ((mn & 7) << 1);
-  const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(img + off));
-  const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(img + off + 4 * 2 * R));
-  typedef __attribute__((ext_vector_type(8))) short v8s;
-  const v8s v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
+// The images' chunk XOR and the fragment read are lds_tr.h's (mn_off<R>, frag_tr<R>).
 
 // DEPTH: register sets of operands in flight -- a step's loads go out DEPTH
 // steps ahead (2: the original two-ahead prefetch; 3: one more set, which the

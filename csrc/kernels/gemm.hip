@@ -20,6 +20,7 @@
 // are remapped so consecutive tiles of one output row band land on one XCD
 // (shared A panel in that XCD's L2).
 #include "common.h"
+#include "gemm_api.h"
 
 #include <algorithm>
 

@@ -44,6 +44,8 @@
 // leading dimensions; an M/N-contiguous operand's M (or N) is a multiple of 8.
 // Row/column tails are clamped (their products only reach unstored outputs).
 #include "common.h"
+#include "gemm_api.h"
+#include "lds_tr.h"
 
 #include <cstdlib>
 
@@ -52,11 +54,6 @@ namespace gemm2 {
 
 constexpr int BN = 256, NTHR = 512;
 constexpr int KQ = 64;   // K granule of the shape contract / split-K chunks
-
-typedef __attribute__((address_space(3))) void lvoid;
-typedef __attribute__((address_space(1))) void gvoid;
-typedef __attribute__((ext_vector_type(4))) short v4s;
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2, ACT_TANH = 3, ACT_GELU = 4 };
 
@@ -111,25 +108,7 @@ __device__ __forceinline__ int kc_off(int r, int c) {
   constexpr int CPR = BK / 8;
   return r * (BK * 2) + ((c ^ ((r / (16 / CPR)) & (CPR - 1))) << 4);
 }
-// M/N-contiguous [BK][R] bf16: byte offset of (k, 16-byte chunk ch = mn/8).
-// A transposed fragment read (frag, ds_read_b64_tr_b16) takes a 32-byte
-// segment from each of 16 k-rows (k = 32 s + {0..3, 8..11, 16..19, 24..27});
-// the chunk XOR spreads them over the bank row.  R >= 128 (rows >= 256 B):
-// k bits 0, 1, 3 pick one of 8 segments.  R = 64 (128-byte rows, two per
-// 256-byte bank row): k bit 0 already picks the half, so the XOR takes bits 1
-// and 3 -- the masked R >= 128 XOR there (2 (k & 3)) collided with bit 0 and
-// left half the banks unused: 2x the LDS cycles of every B read of a 192-wide
-// tile's second quadrant column (SQ_LDS_BANK_CONFLICT 5x, profiles/gemm_layout_ab_r6.txt).
-__device__ __forceinline__ int mn_swz(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-template <int R>
-__device__ __forceinline__ int mn_sw(int k) {
-  if constexpr (R == 64) return (((k >> 1) & 1) | (((k >> 3) & 1) << 1)) << 1;
-  else return (mn_swz(k) << 1) & (R / 8 - 1);
-}
-template <int R>
-__device__ __forceinline__ int mn_off(int k, int ch) {
-  return k * (2 * R) + ((ch ^ mn_sw<R>(k)) << 4);
-}
+// M/N-contiguous [BK][R] bf16: mn_off<R>(k, ch) and its chunk XOR mn_sw<R>(k) are lds_tr.h's.
 
 // Stage one operand tile (R rows of the output dimension x BK k) into `img`.
 // KC: src element (row, k) at base[row * ld + k]; else at base[k * ld + row].
@@ -187,16 +166,7 @@ __device__ __forceinline__ bf16x8 frag(const uint8_t* img, int rb, int s, int la
   if constexpr (KC) {
     return *reinterpret_cast<const bf16x8*>(img + kc_off<BK>(rb + (lane & 15), s * 4 + (lane >> 4)));
   } else {
-    // ds_read_b64_tr_b16: lane 4q+p of a 16-lane group addresses row k0+q,
-    // columns 4p..4p+3 of the 4x16 block; lane i receives column i, row q in q
-    const int k = s * 32 + 8 * (lane >> 4) + ((lane & 15) >> 2);
-    const int mn = rb + 4 * (lane & 3);
-    const int off = mn_off<R>(k, mn >> 3) + ((mn & 7) << 1);
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(img + off));
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(img + off + 4 * 2 * R));
-    typedef __attribute__((ext_vector_type(8))) short v8s;
-    const v8s v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
+    return frag_tr<R>(img, rb, s, lane);
   }
 }
 
@@ -697,7 +667,6 @@ __global__ __launch_bounds__(NTHR) void gemm_8ph(const uint16_t* __restrict__ A,
 #pragma unroll
       for (int q = 0; q < 8; ++q) { cs[q] = 0.f; cq[q] = 0.f; }
     }
-    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
     // DG: the saved pre-activation of BOTH halves requested up front (16 loads
     // in flight; the operand-fragment registers are free after the loop)
     u32x4 apre[DG ? 16 : 1];

@@ -35,6 +35,7 @@
 #include "common.h"
 #include "gstep_kind.h"
 #include "mlp_api.h"
+#include "mlp_device.h"
 
 namespace dtfk {
 namespace gmlp {
@@ -51,26 +52,9 @@ __device__ __forceinline__ float pin(float v) {
   return v;
 }
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float act_fwd(float z, int act) {
-  return act == 0 ? 1.f / (1.f + expf(-z)) : fmaxf(z, 0.f);
-}
-// derivative from the activation's output (sigmoid: a(1-a); relu: a > 0)
-__device__ __forceinline__ float act_bwd(float a, int act) {
-  return act == 0 ? a * (1.f - a) : (a > 0.f ? 1.f : 0.f);
-}
-
 // ---------------------------------------------------------------- L1
 constexpr int L1W = 8;     // waves per a2 tile (interleaved 16-deep K blocks)
 constexpr int PF = 8;      // K blocks per wave whose loads are issued before any MFMA
-
-// A uint8 pixel as the float32 the MNIST loader feeds: k / 255 correctly rounded
-// (numpy's float32 division; data/mnist.py), so a uint8 feed is bit-identical to
-// the float one.
-__device__ __forceinline__ float px255(uint32_t k) { return __fdiv_rn((float)k, 255.f); }
 
 // VEC: K % 4 == 0 and x 16-byte aligned -> x as float4s.  U8: x is uint8 pixels
 // (xu, 4-byte aligned rows, K % 4 == 0), 4 per 32-bit load, converted by px255.

@@ -17,6 +17,7 @@
 //          locking = 1: a compare-and-swap loop per element (no lost updates)
 //          and global_step += 1 (atomic) -> gstep_out.
 #include "common.h"
+#include "ops_api.h"
 
 namespace dtfk {
 namespace hogwild {

@@ -106,7 +106,6 @@ __device__ bool wait_peers(const Coll& c, int ph, u64 s) {
 // loads -- never served from a cache line of this GPU -- several in flight per
 // lane; Coll::wide == 0 (DTF_IPC_NARROW=1, A/B probe) reads 8-byte relaxed
 // system-scope atomics instead.
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 constexpr int SYS = 1 | 16;   // sc0 | sc1
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, long long bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(bytes < 0x7fffffffLL ? bytes : 0x7fffffffLL),

@@ -41,6 +41,7 @@
 // operand pipeline, 16-row workgroups for more waves per SIMD.
 #include "common.h"
 #include "mlp_api.h"
+#include "mlp_device.h"
 
 namespace dtfk {
 namespace mlpe {
@@ -52,19 +53,6 @@ constexpr int ROWS = 16 * RT;
 constexpr int NW = 4;                   // waves: interleaved 16-deep K blocks
 constexpr int LDA = MAXH + 4;           // a2 row stride in LDS (floats)
 constexpr int RED = 256;                // threads of mlp_eval_reduce
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float act_fwd(float z, int act) {
-  return act == 0 ? 1.f / (1.f + expf(-z)) : fmaxf(z, 0.f);
-}
-
-// graph_mlp.hip's px255: a uint8 pixel as the float32 the MNIST loader feeds
-// (k / 255 correctly rounded), so a uint8 evaluation is bit-identical to the
-// float one.
-__device__ __forceinline__ float px255(uint32_t k) { return __fdiv_rn((float)k, 255.f); }
 
 enum { X_F32 = 0, X_F32V = 1, X_U8 = 2 };   // x as floats | float4s (K % 4 == 0, 16-byte aligned) | 4 pixels per load
 

@@ -44,9 +44,6 @@ constexpr int OFF_W2 = 78400, OFF_B1 = 79400, OFF_B2 = 79500, NPARAM = 79510;
 constexpr int KSTEPS = DINP / 32;          // 25
 constexpr int P1N = 1112;                  // [dW2 1000 | (unused 100) | db2 10 | loss | correct]
 constexpr int XTLD = 40;                   // LDS row stride (bf16) of a transposed x tile [64 px][32 batch]
-// register staging in native vectors (an array of HIP's struct uint4 stayed in scratch memory)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ bf16x8 u8x8_to_bf16(u32x2 w) {
   // integers 0..255 are exact in bf16
@@ -61,6 +58,7 @@ __device__ __forceinline__ bf16x8 u8x8_to_bf16(u32x2 w) {
 }
 
 // fp32 -> hi + mid + lo bf16, exact for normal values (8 + 8 + 8 mantissa bits)
+// (mlp_persist_f32.hip's split3 is another function: it truncates each piece, this one rounds to nearest.)
 __device__ __forceinline__ void split3(float v, uint16_t& h, uint16_t& m, uint16_t& l) {
   h = f2bf(v);
   const float r1 = v - bf2f(h);

@@ -120,7 +120,6 @@
 namespace dtfk {
 namespace mlpf {
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((address_space(1))) unsigned gu32;
 
 constexpr int DIN = 784, HID = 100, NCLS = 10;
@@ -305,6 +304,7 @@ struct Args {
 // patterns whose low 16 bits are zero: hi keeps v's top 8 significant bits, the
 // remainder r = v - hi is exact (<= 16 bits), mid keeps its top 8, and r - mid
 // has <= 8 significant bits, so lo is exact too (normal range).  4 VALU ops.
+// (mlp_gemm.hip's split3 is another function: it rounds each piece to nearest, this one truncates.)
 __device__ __forceinline__ void split3(float v, uint32_t& h, uint32_t& m, uint32_t& l) {
   h = __float_as_uint(v) & 0xffff0000u;
   const float r1 = v - __uint_as_float(h);
@@ -350,9 +350,6 @@ __device__ __forceinline__ bf16x8 px8(uint32_t w0, uint32_t w1) {
 #define PROC(wg, k) \
   if constexpr (INS) { PRO(wg, k); }
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ float ub(uint32_t w, int e) { return (float)((w >> (8 * e)) & 0xffu); }
 
 __device__ __forceinline__ void lds_barrier() {   // orders LDS only: no vmcnt(0) on in-flight prefetches
@@ -363,8 +360,6 @@ __device__ __forceinline__ void lds_barrier() {   // orders LDS only: no vmcnt(0
 
 // one lane-linear LDS-DMA piece: lane l's 16 bytes at gsrc land at lds + 16 l
 __device__ __forceinline__ void glds16(const void* gsrc, uint8_t* lds) {
-  typedef __attribute__((address_space(1))) void gvoid;
-  typedef __attribute__((address_space(3))) void lvoid;
   __builtin_amdgcn_global_load_lds((gvoid*)(gsrc), (lvoid*)(lds), 16, 0, 0);
 }
 
@@ -453,7 +448,6 @@ __device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff s
 // zero without touching memory, so the NW loads of a lane stay unconditional
 // (no branch, no wait between them: all in flight at once) and only payload
 // crosses the fabric.
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 constexpr int SYS = 1 | 16;            // sc0 | sc1
 constexpr int OOB_OFF = 0x7ffffff0;
 // one resource per rank, built once per launch in SGPRs (the table entry is read

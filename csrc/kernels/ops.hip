@@ -15,6 +15,7 @@
 // independent, shuffles over 64 lanes, no warp-32 idioms.
 #include "auc_bin.h"
 #include "common.h"
+#include "ops_api.h"
 #include "optim_rules.h"
 
 namespace dtfk {

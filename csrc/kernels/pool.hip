@@ -12,12 +12,10 @@
 // NaN propagates like torch (a NaN wins the window); ties keep the first
 // maximum in (kh, kw) scan order, as torch does.
 #include "common.h"
+#include "pool_api.h"
 
 namespace dtfk {
 namespace pool {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float lo16(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float hi16(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }

@@ -12,6 +12,7 @@
 // sharded table is bit-identical for any world size.  One thread per output
 // element; ~60 integer/float ops per element keep a 1e9-row init HBM-bound.
 #include "common.h"
+#include "ops_api.h"
 
 namespace dtfk {
 namespace rnd {

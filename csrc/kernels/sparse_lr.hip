@@ -55,6 +55,7 @@
 #include "common.h"
 #include "eval_record.h"
 #include "optim_rules.h"
+#include "sparse_lr_api.h"
 
 namespace dtfk {
 namespace slr {

@@ -19,6 +19,7 @@
 // per thread when D % 4 == 0.  `skip` (device int32, may be null): a voided
 // step (sharded-exchange overflow) changes nothing.
 #include "common.h"
+#include "ops_api.h"
 #include "optim_rules.h"
 
 namespace dtfk {

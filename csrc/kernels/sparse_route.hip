@@ -25,6 +25,7 @@
 // owner, the position among that owner's ids), route_scatter writes every
 // output in one pass (threads i >= U also write the -1 padding of slot i).
 #include "common.h"
+#include "ops_api.h"
 
 namespace dtfk {
 namespace route {

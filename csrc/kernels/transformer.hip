@@ -15,6 +15,7 @@
 // Dropout masks are never stored: keep(i) = hash(seed, i) >= p * 2^32 is
 // recomputed in the backward pass from the same (seed, element index).
 #include "common.h"
+#include "transformer_api.h"
 
 #include <cstdlib>
 

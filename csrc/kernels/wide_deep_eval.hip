@@ -69,10 +69,6 @@ namespace wde {
 constexpr int THREADS = 256;
 constexpr int NW = THREADS / 64;
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ long long uni(long long v) {
   const unsigned lo = (unsigned)uni((int)(unsigned)v), hi = (unsigned)uni((int)(v >> 32));
