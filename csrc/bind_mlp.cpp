@@ -69,34 +69,6 @@ void mlp_l1_fwd(at::Tensor x, int64_t x_off, int x_kind, int B, at::Tensor W1T, 
             "mlp_l1_fwd");
 }
 
-// A1 + A2 in one launch (last-arriver row-block handoff); counters: int32[nb], zero at rest
-void mlp_fwd_head(at::Tensor x, int64_t x_off, int x_kind, int B, at::Tensor W1T, at::Tensor z2p, at::Tensor labels,
-                  int64_t labels_off, at::Tensor W2T, at::Tensor W2N, at::Tensor params, at::Tensor dz2T,
-                  at::Tensor partials, double inv_batch, int act, bool naive_loss, at::Tensor counters,
-                  at::Tensor gstep) {
-  if (B <= 0) throw std::runtime_error("B must be positive");
-  const int nb = (B + 15) / 16, BP = bp_of(B);
-  const char* xb = x_ptr(x, x_off, x_kind, B);
-  need(W1T, at::kBFloat16, 112 * 800, "W1T");
-  need(z2p, at::kFloat, (int64_t)dtfk_mlp_ksplit() * nb * 16 * 112, "z2p");
-  if (!labels.is_cuda() || labels.scalar_type() != at::kByte)
-    throw std::runtime_error("labels must be a uint8 GPU tensor");
-  if (labels.numel() < labels_off + B) throw std::runtime_error("labels buffer too small");
-  need(W2T, at::kBFloat16, 16 * 128, "W2T");
-  need(W2N, at::kBFloat16, 112 * 32, "W2N");
-  need(params, at::kFloat, kNParam, "params");
-  need(dz2T, at::kBFloat16, (int64_t)112 * BP, "dz2T");
-  need(partials, at::kFloat, (int64_t)nb * 1112, "partials");
-  need(counters, at::kInt, nb, "counters");
-  hip_check(dtfk_mlp_fwd_head(xb, x_kind, B, W1T.data_ptr(), z2p.data_ptr<float>(),
-                              reinterpret_cast<const uint8_t*>(labels.data_ptr()) + labels_off, W2T.data_ptr(),
-                              W2N.data_ptr(), params.data_ptr<float>(), dz2T.data_ptr(), BP,
-                              partials.data_ptr<float>(), (float)inv_batch, act, naive_loss ? 1 : 0,
-                              counters.data_ptr<int>(), reinterpret_cast<long long*>(gstep.data_ptr<int64_t>()),
-                              cur_stream()),
-            "mlp_fwd_head");
-}
-
 void mlp_head_bwd(at::Tensor z2p, at::Tensor labels, int64_t labels_off, int B, at::Tensor W2T,
                   at::Tensor W2N, at::Tensor params, at::Tensor dz2T, at::Tensor partials, double inv_batch, int act,
                   bool naive_loss, at::Tensor gstep, c10::optional<at::Tensor> ts) {
@@ -377,16 +349,21 @@ struct PersistF32Plan {
   }
 };
 
+// "<who>: fp32 contiguous device <what> expected" unless every tensor is one
+static void need_f32_device(const char* who, std::initializer_list<const at::Tensor*> ts,
+                            const char* what = "parameters") {
+  for (const at::Tensor* t : ts)
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(), who,
+                ": fp32 contiguous device ", what, " expected");
+}
+
 // The compat graph's matched MLP training step (csrc/kernels/graph_mlp.hip).
 // sgd: W/b updated in place with lr; else gradients into g* (same shapes).
 void graph_mlp_step(at::Tensor x, at::Tensor ylab, at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2,
                     at::Tensor a2buf, at::Tensor dz2buf, c10::optional<std::vector<at::Tensor>> grads,
                     at::Tensor metrics,
                     c10::optional<at::Tensor> gstep, double lr, int act, bool naive, bool sgd) {
-  for (const at::Tensor* t : {&x, &ylab, &W1, &b1, &W2, &b2, &a2buf, &dz2buf, &metrics}) {
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
-                "graph_mlp_step: fp32 contiguous device tensors expected");
-  }
+  need_f32_device("graph_mlp_step", {&x, &ylab, &W1, &b1, &W2, &b2, &a2buf, &dz2buf, &metrics}, "tensors");
   TORCH_CHECK(x.dim() == 2 && W1.dim() == 2 && W2.dim() == 2, "graph_mlp_step: 2-D x, W1, W2");
   const int B = (int)x.size(0), K = (int)x.size(1), H = (int)W1.size(1), C = (int)W2.size(1);
   TORCH_CHECK(W1.size(0) == K && W2.size(0) == H && b1.numel() == H && b2.numel() == C &&
@@ -438,10 +415,7 @@ void graph_mlp_step(at::Tensor x, at::Tensor ylab, at::Tensor W1, at::Tensor b1,
 void mlp_eval(at::Tensor x, at::Tensor labels, at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2, int act,
               bool naive, at::Tensor out, bool reset, c10::optional<at::Tensor> pred,
               c10::optional<at::Tensor> logits) {
-  for (const at::Tensor* t : {&W1, &b1, &W2, &b2}) {
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
-                "mlp_eval: fp32 contiguous device parameters expected");
-  }
+  need_f32_device("mlp_eval", {&W1, &b1, &W2, &b2});
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
                   (x.scalar_type() == at::kFloat || x.scalar_type() == at::kByte),
               "mlp_eval: x must be a contiguous 2-D fp32 or uint8 device tensor");
@@ -511,9 +485,7 @@ class GraphStepPlan {
   GraphStepPlan(at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2, c10::optional<at::Tensor> gstep, int B,
                 int act, bool naive, bool use_graph)
       : W1_(W1), b1_(b1), W2_(W2), b2_(b2), use_graph_(use_graph) {
-    for (const at::Tensor* t : {&W1, &b1, &W2, &b2})
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
-                  "GraphStepPlan: fp32 contiguous device parameters expected");
+    need_f32_device("GraphStepPlan", {&W1, &b1, &W2, &b2});
     const int K = (int)W1.size(0), H = (int)W1.size(1), C = (int)W2.size(1);
     TORCH_CHECK(W2.size(0) == H && b1.numel() == H && b2.numel() == C, "GraphStepPlan: shape mismatch");
     const int HP = (H + 16) & ~15, BP = (B + 15) & ~15;
@@ -751,9 +723,7 @@ class ResidentMLPPlan {
   ResidentMLPPlan(at::Tensor W1, at::Tensor b1, at::Tensor W2, at::Tensor b2, c10::optional<at::Tensor> gstep, int B,
                   int act, bool naive, double idle_s, double timeout_s)
       : W1_(W1), b1_(b1), W2_(W2), b2_(b2), B_(B), act_(act), naive_(naive) {
-    for (const at::Tensor* t : {&W1, &b1, &W2, &b2})
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
-                  "ResidentMLPPlan: fp32 contiguous device parameters expected");
+    need_f32_device("ResidentMLPPlan", {&W1, &b1, &W2, &b2});
     TORCH_CHECK(W1.dim() == 2 && W1.size(0) == 784 && W1.size(1) == 100 && b1.numel() == 100 && W2.dim() == 2 &&
                     W2.size(0) == 100 && W2.size(1) == 10 && b2.numel() == 10,
                 "ResidentMLPPlan: the reference's 784-100-10 shapes expected");
@@ -1080,7 +1050,6 @@ void init_mlp(py::module& m) {
         py::arg("ipc_rank") = 0, py::arg("ipc_parity") = 0, py::arg("ipc_slot_bytes") = 0,
         py::arg("ipc_err") = py::none(), py::arg("ipc_timeout_s") = 5.0);
   m.def("mlp_apply_flat", &mlp_apply_flat);
-  m.def("mlp_fwd_head", &mlp_fwd_head);
   m.def("mlp_ipc_reduce_apply", &mlp_ipc_reduce_apply);
   m.def("mlp_ipc_flag_bytes", &dtfk_mlp_ipc_flag_bytes);
   m.def("memcpy_h2d_async", &memcpy_h2d_async);

@@ -126,10 +126,6 @@ extern "C" {
 int dtfk_mlp_ksplit();
 hipError_t dtfk_mlp_l1_fwd(const void* x, int x_kind, int B, const void* W1T, float* z2p, long long* ts,
                            hipStream_t stream);
-hipError_t dtfk_mlp_fwd_head(const void* x, int x_kind, int B, const void* W1T, float* z2p, const void* labels,
-                             const void* W2T, const void* W2N, const float* params, void* dz2T, int BP,
-                             float* partials, float inv_batch, int act, int naive_loss, int* counters,
-                             long long* gstep, hipStream_t stream);
 hipError_t dtfk_mlp_head_bwd(const float* z2p, const void* labels, int B, const void* W2T, const void* W2N,
                              const float* params, void* dz2T, int BP, float* partials, float inv_batch, int act,
                              int naive_loss, long long* gstep, long long* ts, hipStream_t stream);

@@ -2,26 +2,23 @@
 (example.py:69-128; sigmoid hidden layer, softmax output, mean cross-entropy,
 GradientDescentOptimizer(0.0005), batch 100 per worker).
 
-Three implementations of the same step, and one evaluation:
-
 * `reference_step`   -- plain PyTorch fp32 (the numerics oracle for the HIP
                         kernels, and the CPU/gloo path of BASELINE config #1).
 * `MLP` (nn.Module)  -- generic path built from the framework ops
                         (`ops.linear_act`, `ops.softmax_xent`), used by the
                         TF-compat session layer and autograd users.
-* `FusedMLPTrainer`  -- the MI355X hot path: 2 kernels per step on 1 GPU, or
-                        2 kernels + one RCCL all-reduce + the flat SGD kernel
-                        in sync data parallel (csrc/kernels/mlp_step.hip),
-                        replayed from hipGraphs by `MLPStepRunner` with the
-                        input streamed from pinned host memory on a side stream.
-* `evaluate`         -- held-out loss / accuracy (example.py:187), forward only:
-                        the exact-fp32 MFMA kernel of csrc/kernels/mlp_eval.hip
-                        over uint8 or float rows, ids or one-hot labels, on a
-                        flat master or four separate tensors; host arrays are
-                        copied chunk by chunk on a side stream under the
-                        previous chunk's kernel and accumulated on the device
-                        (one read-back).  Also
-                        `FusedMLPTrainer.evaluate` / `GemmMLPTrainer.evaluate`
+* `MLPTrainer`       -- one rank's device state (fp32 master, lr, metrics ring,
+                        global step) and its two step engines:
+                        `FusedMLPTrainer` (csrc/kernels/mlp_step.hip, 3 launches
+                        per step, batch ~100) and `GemmMLPTrainer`
+                        (csrc/kernels/mlp_gemm.hip, large batch).
+* `MLPStepRunner`    -- replays either trainer's step from hipGraphs over a
+                        pinned-host epoch; `PersistentMLPRunner` -- the
+                        headline: one persistent launch per chunk of steps
+                        (csrc/kernels/mlp_persist_f32.hip).  What they launch
+                        next is planned in `mlp_plan.py`.
+* `evaluate`         -- held-out loss / accuracy (example.py:187), forward only
+                        (csrc/kernels/mlp_eval.hip); also `MLPTrainer.evaluate`
                         on the trainer's own master.  CPU parameters: PyTorch.
 
 Parameter layout (flat fp32, TF variable order and names):
@@ -30,16 +27,15 @@ Parameter layout (flat fp32, TF variable order and names):
 """
 from __future__ import annotations
 
-import math
 import os
-import time
 from collections import OrderedDict
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
 from .. import _native
+from .mlp_plan import StagePlanner, chunks
 
 D_IN, HIDDEN, N_CLS = 784, 100, 10
 OFF_W1, OFF_W2, OFF_B1, OFF_B2 = 0, 78400, 79400, 79500
@@ -288,48 +284,89 @@ class MLP(torch.nn.Module):
         return linear_act(a2, self.W2, self.b2, "none")
 
 
-class FusedMLPTrainer:
-    """One rank's fused MLP training step (see module doc)."""
+class MLPTrainer:
+    """One rank's training state on the device: the flat fp32 master, the
+    learning rate, the (loss, accuracy) ring and the global step.  An engine adds
+    its scratch buffers, `refresh_shadows` (whatever it derives from the master),
+    `enqueue_step` and `step_tensors`, and ends its constructor with `set_params`."""
+
+    def __init__(self, batch_size: int, lr: float, act: str, world, naive_loss: bool, metrics_ring: int, device):
+        self.C = _native.load()
+        self.world = world
+        self.world_size = 1 if world is None else world.world_size
+        self.device = dev = device or torch.device("cuda", torch.cuda.current_device())
+        self.B = int(batch_size)
+        self.act = ACTS[act]
+        self.act_name = act
+        self.naive = bool(naive_loss)
+        self.params = torch.zeros(NPARAM, dtype=torch.float32, device=dev)
+        self.lr = torch.tensor([lr], dtype=torch.float32, device=dev)
+        self.ring = int(metrics_ring)
+        self.metrics = torch.zeros(self.ring * 2, dtype=torch.float32, device=dev)
+        self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.allreduce = "none"
+        self.ipc_parity = 0          # exchange slot of the next step (`MLPStepRunner` plans it per graph)
+        self.shadows_stale = False   # set by PersistentMLPRunner (it updates only the fp32 master)
+
+    def ipc_error(self) -> int:
+        return 0
+
+    def set_params(self, flat_cpu: torch.Tensor, broadcast: bool = True):
+        self.params.copy_(flat_cpu.to(self.device, torch.float32))
+        if broadcast and self.world is not None and self.world_size > 1:
+            self.world.broadcast(self.params, 0)  # chief init + broadcast (SURVEY A6)
+        self.refresh_shadows()
+
+    def get_params(self) -> torch.Tensor:
+        return self.params.detach().cpu()
+
+    def set_lr(self, lr: float):
+        self.lr.fill_(lr)
+
+    @property
+    def global_step(self) -> int:
+        return int(self.gstep.item())
+
+    def set_global_step(self, v: int):
+        self.gstep.fill_(int(v))
+
+    def read_metrics(self, first_step: int, last_step: int) -> np.ndarray:
+        """(loss, accuracy) rows for global steps [first, last)."""
+        m = self.metrics.view(self.ring, 2).cpu().numpy()
+        return m[np.arange(first_step, last_step) % self.ring]
+
+    def evaluate(self, x, labels, **kw):
+        """`evaluate` on this trainer's fp32 master with its activation and loss
+        form, on the current stream behind the steps already queued (a call after
+        `PersistentMLPRunner.run` sees the trained parameters).  Changes nothing:
+        parameters, global_step and the metrics ring stay as they are."""
+        return evaluate(self.params, x, labels, act=self.act_name, naive=self.naive, **kw)
+
+
+class FusedMLPTrainer(MLPTrainer):
+    """The small-batch step (csrc/kernels/mlp_step.hip): 3 launches on 1 GPU
+    (`mlp_l1_fwd`, `mlp_head_bwd`, `mlp_wgrad` with SGD in its epilogue); in sync
+    data parallel the gradient exchange inside `mlp_wgrad` over IPC ("ipc-fused"),
+    after it over IPC ("ipc-apply") or RCCL, or left to the caller ("external")."""
 
     def __init__(self, batch_size: int = 100, lr: float = 0.0005, act: str = "sigmoid",
                  world=None, grad_dtype: torch.dtype = torch.bfloat16, naive_loss: bool = False,
                  metrics_ring: int = 8192, seed: int = 1, device=None, allreduce: str = "auto",
                  ipc_timeout_s: float = 5.0):
-        self.C = _native.load()
-        self.world = world
-        self.world_size = 1 if world is None else world.world_size
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        dev = self.device
-        B = int(batch_size)
-        self.B = B
+        super().__init__(batch_size, lr, act, world, naive_loss, metrics_ring, device)
+        dev, B, bf = self.device, self.B, torch.bfloat16
         self.nb = (B + 15) // 16
-        self.BP = ((B + 31) // 32) * 32
-        self.act = ACTS[act]
-        self.act_name = act
-        self.naive = bool(naive_loss)
-        bf = torch.bfloat16
-        self.params = torch.zeros(NPARAM, dtype=torch.float32, device=dev)
         self.W1T = torch.zeros(112 * 800, dtype=bf, device=dev)
         self.W2T = torch.zeros(16 * 128, dtype=bf, device=dev)
         self.W2N = torch.zeros(112 * 32, dtype=bf, device=dev)
         self.z2p = torch.zeros(self.C.mlp_ksplit() * self.nb * 16 * 112, dtype=torch.float32,
                                device=dev)
-        self.dz2T = torch.zeros(112 * self.BP, dtype=bf, device=dev)
+        self.dz2T = torch.zeros(112 * ((B + 31) // 32) * 32, dtype=bf, device=dev)
         self.partials = torch.zeros(self.nb * 1112, dtype=torch.float32, device=dev)
         self.grad_dtype = grad_dtype
         self.grads = (torch.zeros(NPARAM, dtype=grad_dtype, device=dev)
                       if self.world_size > 1 else None)
-        self.lr = torch.tensor([lr], dtype=torch.float32, device=dev)
-        self.ring = int(metrics_ring)
-        self.metrics = torch.zeros(self.ring * 2, dtype=torch.float32, device=dev)
-        self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.counters = torch.zeros(max(64, self.nb), dtype=torch.int32, device=dev)
-        # A1+A2 merged by last-arriver handoff: correct, but measured 13.56 vs 13.16 us/step
-        # for the split pair on MI355X (the split boundary is cheaper than the handoff), so opt-in
-        self.merged_head = os.environ.get("DTF_MLP_MERGED_HEAD", "0") == "1"
-        self.allreduce = "none"
         self.ipc = None
-        self.ipc_parity = 0
         self.ipc_mode = None
         self.ipc_timeout_s = float(ipc_timeout_s)
         if self.world_size > 1 and allreduce == "external":
@@ -357,7 +394,6 @@ class FusedMLPTrainer:
         # sharing one GPU in tests) does not
         self.graph_safe = (self.world_size == 1 or self.allreduce.startswith("ipc")
                            or (world is not None and world.comm is not None))
-        self.shadows_stale = False   # set by PersistentMLPRunner (it updates only the fp32 master)
         self.set_params(init_params(seed))
 
     # ---------------------------------------------------------------- IPC one-shot all-reduce
@@ -379,35 +415,9 @@ class FusedMLPTrainer:
     def ipc_error(self) -> int:
         return int(self.ipc_err.item()) if self.ipc is not None else 0
 
-    # ---------------------------------------------------------------- state
-    def set_params(self, flat_cpu: torch.Tensor, broadcast: bool = True):
-        self.params.copy_(flat_cpu.to(self.device, torch.float32))
-        if broadcast and self.world is not None and self.world_size > 1:
-            self.world.broadcast(self.params, 0)  # chief init + broadcast
-        self.refresh_shadows()
-
     def refresh_shadows(self):
         self.C.mlp_apply_flat(self.params, None, self.lr, 0.0, self.W1T, self.W2T, self.W2N)
         self.shadows_stale = False
-
-    def get_params(self) -> torch.Tensor:
-        return self.params.detach().cpu()
-
-    def set_lr(self, lr: float):
-        self.lr.fill_(lr)
-
-    @property
-    def global_step(self) -> int:
-        return int(self.gstep.item())
-
-    def set_global_step(self, v: int):
-        self.gstep.fill_(int(v))
-
-    def read_metrics(self, first_step: int, last_step: int) -> np.ndarray:
-        """(loss, accuracy) rows for global steps [first, last)."""
-        m = self.metrics.view(self.ring, 2).cpu().numpy()
-        idx = np.arange(first_step, last_step) % self.ring
-        return m[idx]
 
     # ----------------------------------------------------------------- steps
     def enqueue_step(self, x: torch.Tensor, x_off: int, x_kind: int, labels: torch.Tensor,
@@ -420,17 +430,16 @@ class FusedMLPTrainer:
         C, B = self.C, self.B
         if self.shadows_stale:
             self.refresh_shadows()
-        if self.merged_head:   # A1+A2 in one launch (last-arriver handoff per row block)
-            C.mlp_fwd_head(x, x_off, x_kind, B, self.W1T, self.z2p, labels, labels_off, self.W2T, self.W2N,
-                           self.params, self.dz2T, self.partials, 1.0 / B, self.act, self.naive, self.counters,
-                           self.gstep)
-        else:
-            C.mlp_l1_fwd(x, x_off, x_kind, B, self.W1T, self.z2p)
-            C.mlp_head_bwd(self.z2p, labels, labels_off, B, self.W2T, self.W2N, self.params, self.dz2T,
-                           self.partials, 1.0 / B, self.act, self.naive, self.gstep)
+        C.mlp_l1_fwd(x, x_off, x_kind, B, self.W1T, self.z2p)
+        C.mlp_head_bwd(self.z2p, labels, labels_off, B, self.W2T, self.W2N, self.params, self.dz2T,
+                       self.partials, 1.0 / B, self.act, self.naive, self.gstep)
+
+        def wgrad(grads, grad_kind, *ipc_tail):
+            C.mlp_wgrad(x, x_off, x_kind, self.dz2T, B, self.partials, self.params, self.W1T, self.W2T, self.W2N,
+                        grads, grad_kind, self.lr, self.metrics, self.gstep, *ipc_tail)
+
         if self.world_size == 1:
-            C.mlp_wgrad(x, x_off, x_kind, self.dz2T, B, self.partials, self.params, self.W1T,
-                        self.W2T, self.W2N, None, 0, self.lr, self.metrics, self.gstep)
+            wgrad(None, 0)
         elif self.ipc is not None:
             par = self.ipc_parity if ipc_parity is None else int(ipc_parity) & 1
             if ipc_parity is None:
@@ -438,22 +447,17 @@ class FusedMLPTrainer:
             if self.ipc_mode == "fused":
                 # every wgrad workgroup swaps its gradient block with the same workgroup
                 # on all peers (IPC over xGMI) and applies SGD in place: 3 launches/step
-                C.mlp_wgrad(x, x_off, x_kind, self.dz2T, B, self.partials, self.params, self.W1T,
-                            self.W2T, self.W2N, None, 3, self.lr, self.metrics, self.gstep, None,
-                            self.ipc.table_ptr(), self.world_size, self.world.rank, par, self.ipc_slot,
-                            self.ipc_err, self.ipc_timeout_s)
+                wgrad(None, 3, None, self.ipc.table_ptr(), self.world_size, self.world.rank, par, self.ipc_slot,
+                      self.ipc_err, self.ipc_timeout_s)
             else:
                 # one-shot: bf16 grads into this rank's exported slot, then every rank
                 # sums all peers' slots over xGMI inside the SGD apply kernel
-                C.mlp_wgrad(x, x_off, x_kind, self.dz2T, B, self.partials, self.params, self.W1T,
-                            self.W2T, self.W2N, self.ipc_grads[par], 2, self.lr, self.metrics, self.gstep)
+                wgrad(self.ipc_grads[par], 2)
                 C.mlp_ipc_reduce_apply(self.params, self.ipc.table_ptr(), self.world_size, self.world.rank, par,
                                        self.ipc_slot, self.gstep, self.lr, 1.0 / self.world_size, self.W1T,
                                        self.W2T, self.W2N, self.ipc_err, self.ipc_timeout_s)
         else:
-            kind = 1 if self.grad_dtype == torch.float32 else 2
-            C.mlp_wgrad(x, x_off, x_kind, self.dz2T, B, self.partials, self.params, self.W1T,
-                        self.W2T, self.W2N, self.grads, kind, self.lr, self.metrics, self.gstep)
+            wgrad(self.grads, 1 if self.grad_dtype == torch.float32 else 2)
             self.world.all_reduce(self.grads, "sum")
             C.mlp_apply_flat(self.params, self.grads, self.lr, 1.0 / self.world_size, self.W1T,
                              self.W2T, self.W2N)
@@ -463,15 +467,8 @@ class FusedMLPTrainer:
         kind = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}[x.dtype]
         self.enqueue_step(x.contiguous(), 0, kind, labels.to(torch.uint8).contiguous(), 0)
 
-    def evaluate(self, x, labels, **kw):
-        """`evaluate` on this trainer's fp32 master with its activation and loss
-        form, on the current stream behind the steps already queued (a call after
-        `PersistentMLPRunner.run` sees the trained parameters).  Changes nothing:
-        parameters, global_step and the metrics ring stay as they are."""
-        return evaluate(self.params, x, labels, act=self.act_name, naive=self.naive, **kw)
 
-
-class GemmMLPTrainer:
+class GemmMLPTrainer(MLPTrainer):
     """Large-batch step of the same model (csrc/kernels/mlp_gemm.hip), 4
     launches: `mlpg_l1` (one workgroup per 64 rows x 16 hidden units: the
     hidden layer on bf16 MFMA with W1 as an exact 3-way bf16 split) and
@@ -483,40 +480,24 @@ class GemmMLPTrainer:
     one wave per weight tile: right at B=100, 4x too slow at B=4096.  All three
     launches are graph-capturable, so `MLPStepRunner` replays them exactly like
     the fused trainer's.  N > 1: the apply kernel first writes the reduced flat
-    fp32 gradient, one RCCL all-reduce, then the apply.
-
-    Same interface as `FusedMLPTrainer` (params / metrics ring / global step)."""
+    fp32 gradient, one RCCL all-reduce, then the apply."""
 
     def __init__(self, batch_size: int = 4096, lr: float = 0.0005, act: str = "sigmoid", world=None,
                  naive_loss: bool = False, metrics_ring: int = 8192, seed: int = 1, device=None,
                  **_ignored):
-        self.C = _native.load()
-        self.world = world
-        self.world_size = 1 if world is None else world.world_size
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        dev = self.device
-        B = self.B = int(batch_size)
-        self.BP = (B + 63) // 64 * 64
-        self.act = ACTS[act]
-        self.act_name = act
-        self.naive = bool(naive_loss)
-        f32 = torch.float32
+        super().__init__(batch_size, lr, act, world, naive_loss, metrics_ring, device)
+        dev, B, f32 = self.device, self.B, torch.float32
+        BP = (B + 63) // 64 * 64
         # dW1: one workgroup per (64-pixel block, 128- or 256-row batch chunk); the
         # B-fragment image of dz2 is padded (with zeros) to whole chunks
         wc = self.C.mlpg_wchunk(B)
         self.nchunk = (B + wc - 1) // wc
-        self.params = torch.zeros(NPARAM, dtype=f32, device=dev)
         self.W1S = torch.zeros(3 * 112 * 800, dtype=torch.bfloat16, device=dev)
         self.dz2S = torch.zeros(3 * 112 * self.nchunk * wc, dtype=torch.bfloat16, device=dev)
-        self.a2 = torch.zeros(self.BP * 112, dtype=f32, device=dev)
-        self.P1 = torch.zeros(self.BP // 16 * self.C.mlpg_p1_floats(), dtype=f32, device=dev)
+        self.a2 = torch.zeros(BP * 112, dtype=f32, device=dev)
+        self.P1 = torch.zeros(BP // 16 * self.C.mlpg_p1_floats(), dtype=f32, device=dev)
         self.P2 = torch.zeros(self.nchunk * self.C.mlpg_p2_floats(), dtype=f32, device=dev)
         self.grads = torch.zeros(NPARAM, dtype=f32, device=dev) if self.world_size > 1 else None
-        self.lr = torch.tensor([lr], dtype=f32, device=dev)
-        self.ring = int(metrics_ring)
-        self.metrics = torch.zeros(self.ring * 2, dtype=f32, device=dev)
-        self.gstep = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.allreduce = "none"
         if self.world_size > 1:
             coll = world.gpu_coll(NPARAM * 4)    # collective: IPC on one node, else RCCL; None on gloo worlds
             self.allreduce = "ipc" if (coll is not None and coll is world.ipc) else \
@@ -524,42 +505,14 @@ class GemmMLPTrainer:
         # RCCL and the IPC collectives capture into hipGraphs (the IPC sequence
         # numbers live on the device); a gloo all-reduce does not
         self.graph_safe = self.world_size == 1 or self.allreduce in ("rccl", "ipc")
-        self.ipc_parity = 0
-        self.shadows_stale = False
         self.set_params(init_params(seed))
-
-    def ipc_error(self) -> int:
-        return 0
 
     def _apply(self, mode: int, gin=None, gout=None, scale: float = 1.0):
         self.C.mlpg_apply(self.params, self.P1, self.P2, self.nchunk, gin, gout, self.lr, scale, self.W1S,
                           self.metrics, self.gstep, self.B, mode)
 
-    def set_params(self, flat_cpu: torch.Tensor, broadcast: bool = True):
-        self.params.copy_(flat_cpu.to(self.device, torch.float32))
-        if broadcast and self.world is not None and self.world_size > 1:
-            self.world.broadcast(self.params, 0)
-        self.refresh_shadows()
-
     def refresh_shadows(self):
         self._apply(3)
-
-    def get_params(self) -> torch.Tensor:
-        return self.params.detach().cpu()
-
-    def set_lr(self, lr: float):
-        self.lr.fill_(lr)
-
-    @property
-    def global_step(self) -> int:
-        return int(self.gstep.item())
-
-    def set_global_step(self, v: int):
-        self.gstep.fill_(int(v))
-
-    def read_metrics(self, first_step: int, last_step: int) -> np.ndarray:
-        m = self.metrics.view(self.ring, 2).cpu().numpy()
-        return m[np.arange(first_step, last_step) % self.ring]
 
     def enqueue_step(self, x: torch.Tensor, x_off: int, x_kind: int, labels: torch.Tensor,
                      labels_off: int, ipc_parity: Optional[int] = None):
@@ -583,13 +536,9 @@ class GemmMLPTrainer:
             raise ValueError("GemmMLPTrainer.step_tensors takes uint8 pixels")
         self.enqueue_step(x.contiguous().view(-1), 0, 0, labels.to(torch.uint8).contiguous(), 0)
 
-    def evaluate(self, x, labels, **kw):
-        """`evaluate` on this trainer's fp32 master (see `FusedMLPTrainer.evaluate`)."""
-        return evaluate(self.params, x, labels, act=self.act_name, naive=self.naive, **kw)
-
 
 class MLPStepRunner:
-    """Drives `FusedMLPTrainer` over a pinned-host epoch.
+    """Drives either trainer's `enqueue_step` over a pinned-host epoch.
 
     The epoch lives batch-major in pinned host memory; the device holds only a
     *chunk* stage of `g` batches (g*78.5 KB at B=100).  Each chunk is one
@@ -607,7 +556,7 @@ class MLPStepRunner:
         cross-queue waits are cheap.
     """
 
-    def __init__(self, trainer: FusedMLPTrainer, epoch, steps_per_graph: int = 50,
+    def __init__(self, trainer: MLPTrainer, epoch, steps_per_graph: int = 50,
                  use_graph: bool = True, prefetch: str = "serial"):
         if prefetch not in ("serial", "side"):
             raise ValueError("prefetch must be 'serial' or 'side'")
@@ -619,7 +568,7 @@ class MLPStepRunner:
         self.g = int(max(1, steps_per_graph))
         self.use_graph = use_graph
         self.prefetch = prefetch
-        self.side = torch.cuda.Stream(device=trainer.device)
+        self.side = None       # (side) the copy stream, made by the first run()
         self.graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         nbuf = 2 if prefetch == "side" else 1
         self.stage = [torch.zeros(self.g * epoch.rec, dtype=torch.uint8, device=trainer.device)
@@ -667,21 +616,11 @@ class MLPStepRunner:
             self.graphs[key] = gr
         return gr
 
-    def _chunks(self, cursor: int, steps: int) -> List[Tuple[int, int]]:
-        out, left = [], steps
-        nb = self.epoch.num_batches
-        while left > 0:
-            b0 = cursor % nb
-            g = min(self.g, left)
-            out.append((b0, g))
-            cursor += g
-            left -= g
-        return out
-
     def plan(self, steps: int):
         """[(b0, g, parity, next, ipc_parity)] for the next `steps` steps from the cursor."""
-        ch = self._chunks(self.cursor, steps)
-        after = self._chunks(self.cursor + steps, self.g)[0]  # speculative prefetch
+        nb = self.epoch.num_batches
+        ch = chunks(self.cursor, steps, self.g, nb, wrap=True)
+        after = chunks(self.cursor + steps, self.g, self.g, nb, wrap=True)[0]  # speculative prefetch
         out, par, ipar = [], self.parity, self.t.ipc_parity
         for j, (b0, g) in enumerate(ch):
             nxt = ch[j + 1] if j + 1 < len(ch) else after
@@ -701,6 +640,8 @@ class MLPStepRunner:
 
     def run(self, steps: int, events: Optional[list] = None):
         main = torch.cuda.current_stream()
+        if self.prefetch == "side" and self.side is None:
+            self.side = torch.cuda.Stream(device=self.t.device)
         for (b0, g, par, nxt, ipar) in self.plan(steps):
             key = self._key(b0, g, par, ipar)
             self.t.ipc_parity = (ipar + g) & 1
@@ -755,12 +696,9 @@ class PersistentMLPRunner:
     memory over PCIe into the other device stage while the compute workgroups
     run this one.  No second stream, no cross-queue events, no graph capture.
 
-    Staging is range-based: a request whose steps lie inside a staged chunk
-    runs from it at an offset (no copy).  The chunk prefetched inside a launch
-    is the next planned chunk, or -- for the last launch of a `run()` -- a
-    speculative chunk of the same length as that `run()` (`lookahead` overrides
-    it, e.g. a warmup priming exactly the timed run), so a short timed run never
-    streams more than it computes.  `copy_only_launches` counts cold starts.
+    Which chunk a launch runs and which it copies is `mlp_plan.StagePlanner`'s
+    business (`lookahead`: e.g. a warmup priming exactly the timed run); its
+    `cursor`, `staged`, `copy_only_launches` and `last_prefetch_steps` read here.
 
     N GPUs of one node (world_size > 1): every compute workgroup exchanges its
     gradient with the same workgroup on every peer through IPC-mapped uncached
@@ -781,8 +719,6 @@ class PersistentMLPRunner:
         if precision not in ("fp32", "fp32-mfma"):
             raise ValueError("precision must be 'fp32' or 'fp32-mfma'")
         self.precision = precision
-        self.f32 = True
-        self.mfma_split = precision == "fp32"
         if exchange not in ("one-shot", "two-shot"):
             raise ValueError("exchange must be 'one-shot' or 'two-shot'")
         # N GPUs: one-shot = each workgroup reads its gradient slot from every
@@ -794,11 +730,9 @@ class PersistentMLPRunner:
             raise ValueError(f"PersistentMLPRunner needs batch <= {maxb}")
         if epoch.batch_size != trainer.B:
             raise ValueError("epoch batch size != trainer batch size")
-        self.t = trainer
+        self.t = t = trainer
         self.epoch = epoch
         self.g = int(min(steps_per_launch, epoch.num_batches))
-        self.timeout_s = float(timeout_s)
-        self.grad_bf16 = bool(grad_bf16)
         if placement == "auto":
             # several ranks sharing one GPU (tests): their compute workgroups cannot all sit on one XCD
             nloc = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
@@ -806,30 +740,40 @@ class PersistentMLPRunner:
         if placement not in ("packed", "spread"):
             raise ValueError("placement must be 'auto', 'packed' or 'spread'")
         self.placement = placement
-        dev = trainer.device
-        self.rec_s = int(C.mlpf_stage_rec())
-        self.stages = [torch.zeros(self.g * self.rec_s, dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.xbuf = torch.zeros(int(C.mlpf_xbuf_bytes()), dtype=torch.uint8, device=dev)
-        self.seq = torch.zeros(1, dtype=torch.int64, device=dev)
+        dev = t.device
+        stages = [torch.zeros(self.g * int(C.mlpf_stage_rec()), dtype=torch.uint8, device=dev) for _ in range(2)]
+        xbuf = torch.zeros(int(C.mlpf_xbuf_bytes()), dtype=torch.uint8, device=dev)
+        seq = torch.zeros(1, dtype=torch.int64, device=dev)
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
         self.step_ts = torch.zeros(self.TS_RING, dtype=torch.int64, device=dev)
-        self._phase_ts = None   # fp32 engine: optional [64 steps][64 wg][16] phase stamps (profiling): `phase_ts`
-        self._plan = None       # fp32 engine: prepared C++ launcher (PersistF32Plan)
-        self.cursor = 0
-        self.staged: List[Optional[Tuple[int, int]]] = [None, None]   # (b0, g) resident per stage buffer
-        self.copy_only_launches = 0
-        self.last_prefetch_steps = 0
+        self._phase_ts = None   # optional [64 steps][64 wg][16] phase stamps (profiling): `phase_ts`
         self.use_graph = False  # MLPStepRunner interface
         self.prefetch = "in-kernel"
         self.ipc = None
-        self.W, self.rank = 1, 0
-        w = trainer.world
+        W, rank = 1, 0
+        w = t.world
         if w is not None and w.world_size > 1:
             if int(os.environ.get("LOCAL_WORLD_SIZE", w.world_size)) != w.world_size:
                 raise RuntimeError("the persistent N-GPU exchange needs all ranks on one node")
             from ..parallel.world import open_peer_buffers
             self.ipc = open_peer_buffers(C, int(C.mlpf_ipc_bytes()), w)
-            self.W, self.rank = w.world_size, w.rank
+            W, rank = w.world_size, w.rank
+        # the prepared C++ launcher: every tensor checked and every pointer resolved once (it keeps
+        # the stages, xbuf and seq alive), so a launch is a call with 5 ints
+        self._plan = C.PersistF32Plan(
+            stages[0], stages[1], epoch.rec, t.B, t.params, t.lr, t.metrics, t.gstep, seq, xbuf, self.err,
+            float(timeout_s), t.act, int(t.naive), epoch.host, self.step_ts,
+            self.ipc.table_ptr() if self.ipc is not None else 0, W, rank, bool(grad_bf16),
+            placement == "spread", exchange == "two-shot", precision == "fp32")
+        self._stage = StagePlanner(epoch.num_batches, epoch.rec, self.g, self._plan.launch)
+        self.prepare = self._stage.prepare          # stage the first chunk of the next run(steps), untimed
+        self.invalidate = self._stage.invalidate    # after re-packing the pinned epoch (a shuffle)
+
+    # the staging state lives in the planner (`cursor` and `staged` may be assigned)
+    cursor = property(lambda self: self._stage.cursor, lambda self, v: setattr(self._stage, "cursor", v))
+    staged = property(lambda self: self._stage.staged, lambda self, v: setattr(self._stage, "staged", v))
+    copy_only_launches = property(lambda self: self._stage.copy_only_launches)
+    last_prefetch_steps = property(lambda self: self._stage.last_prefetch_steps)
 
     @property
     def phase_ts(self):
@@ -839,128 +783,25 @@ class PersistentMLPRunner:
     def phase_ts(self, ts):
         """Phase stamps on (an int64 [65*64*16] device tensor: the launches then run
         the instrumented build) or off (None)."""
-        if self._plan is not None:
-            self._plan.set_phase_ts(ts)
+        self._plan.set_phase_ts(ts)
         self._phase_ts = ts
-
-    def _chunks(self, cursor: int, steps: int) -> List[Tuple[int, int]]:
-        out, left = [], steps
-        nb = self.epoch.num_batches
-        while left > 0:
-            b0 = cursor % nb
-            g = min(self.g, left, nb - b0)
-            out.append((b0, g))
-            cursor += g
-            left -= g
-        return out
-
-    def _launch(self, par: int, off: int, nsteps: int, nxt: Tuple[int, int]):
-        """Run `nsteps` from stage `par` at step offset `off`; copy `nxt` into stage par^1."""
-        t, ep = self.t, self.epoch
-        if self._plan is None:   # every pointer resolved once (host-side launch cost)
-            self._plan = t.C.PersistF32Plan(
-                self.stages[0], self.stages[1], ep.rec, t.B, t.params, t.lr, t.metrics, t.gstep, self.seq,
-                self.xbuf, self.err, self.timeout_s, t.act, int(t.naive), ep.host, self.step_ts,
-                self.ipc.table_ptr() if self.ipc is not None else 0, self.W, self.rank, self.grad_bf16,
-                self.placement == "spread", self.exchange == "two-shot", self.mfma_split)
-            self._plan.set_phase_ts(self._phase_ts)
-        self._plan.launch(par, off if nsteps > 0 else 0, nsteps, nxt[0] * ep.rec, nxt[1])
-        if nxt[1] > 0:
-            self.staged[par ^ 1] = nxt
-        self.last_prefetch_steps = nxt[1]
-
-    def _locate(self, b0: int, g: int) -> Optional[Tuple[int, int]]:
-        for par in (0, 1):
-            s = self.staged[par]
-            if s is not None and s[0] <= b0 and b0 + g <= s[0] + s[1]:
-                return par, b0 - s[0]
-        return None
-
-    def _ensure(self, b0: int, g: int) -> Tuple[int, int]:
-        """(stage, offset) holding steps [b0, b0+g); copy-only launch on a miss."""
-        loc = self._locate(b0, g)
-        if loc is None:
-            # cold start / plan change: copy (b0, g) into a stage buffer with a
-            # copy-only launch (the stage it "runs" from is untouched)
-            dst = 0 if self.staged[0] is None else (1 if self.staged[1] is None else 0)
-            par = dst ^ 1
-            self._launch(par, 0, 0, (b0, g))
-            self.copy_only_launches += 1
-            loc = (par ^ 1, 0)
-        return loc
-
-    def prepare(self, steps: int):
-        """Stage the first chunk of the next `run(steps)` (outside any timed region)."""
-        b0, g = self._chunks(self.cursor, steps)[0]
-        self._ensure(b0, g)
-
-    def invalidate(self):
-        """Forget staged chunks (call after re-packing the pinned epoch, e.g. a shuffle)."""
-        self.staged = [None, None]
 
     def error(self) -> int:
         return int(self.err.item())
 
     def run(self, steps: int, events: Optional[list] = None, lookahead: Optional[int] = None):
-        if events is None and self._plan is not None and self._run_fast(steps, lookahead):
-            return
-        main = torch.cuda.current_stream()
-        ch = self._chunks(self.cursor, steps)
-        la = min(self.g, steps if lookahead is None else int(lookahead))
-        for k, (b0, g) in enumerate(ch):
-            if k + 1 < len(ch):
-                nxt = ch[k + 1]
-            else:
-                nxt = self._chunks(self.cursor + g, la)[0] if la > 0 else (0, 0)
-            par, off = self._ensure(b0, g)
-            if nxt[1] > 0 and self.staged[par ^ 1] is not None and self._covers(self.staged[par ^ 1], nxt):
-                nxt_copy = (nxt[0], 0)      # already resident in the other stage: nothing to stream
-            else:
-                nxt_copy = nxt
-            self._launch(par, off, g, nxt_copy)
-            if events is not None:
+        """The next `steps` steps (`StagePlanner.run`); `events` receives one
+        (timing event, steps) pair per compute launch."""
+        record = None
+        if events is not None:
+            main = torch.cuda.current_stream()
+
+            def record(n):
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record(main)
-                events.append((ev, g))
-            self.cursor += g
+                events.append((ev, n))
+        self._stage.run(steps, lookahead, record)
         self.t.shadows_stale = True
-
-    def _run_fast(self, steps: int, lookahead: Optional[int]) -> bool:
-        """run() for the common case -- one chunk, already staged, the resolved
-        launch plan -- with the least host work in front of the launch (the
-        host call is inside a short timed run: ~14 us through the general path).
-        Same launch and bookkeeping as the general path; False when it does not apply."""
-        nb = self.epoch.num_batches
-        b0 = self.cursor % nb
-        if steps <= 0 or steps > self.g or b0 + steps > nb or self._phase_ts is not None:
-            return False
-        s0, s1 = self.staged
-        if s0 is not None and s0[0] <= b0 and b0 + steps <= s0[0] + s0[1]:
-            par, off = 0, b0 - s0[0]
-        elif s1 is not None and s1[0] <= b0 and b0 + steps <= s1[0] + s1[1]:
-            par, off = 1, b0 - s1[0]
-        else:
-            return False
-        la = min(self.g, steps if lookahead is None else int(lookahead))
-        nxt = (0, 0)
-        if la > 0:
-            c = (self.cursor + steps) % nb
-            nxt = (c, min(self.g, la, nb - c))
-            o = self.staged[par ^ 1]
-            if o is not None and o[0] <= nxt[0] and nxt[0] + nxt[1] <= o[0] + o[1]:
-                nxt = (nxt[0], 0)             # already resident in the other stage
-        rec = self.epoch.rec
-        self._plan.launch(par, off, steps, nxt[0] * rec, nxt[1])
-        if nxt[1] > 0:
-            self.staged[par ^ 1] = nxt
-        self.last_prefetch_steps = nxt[1]
-        self.cursor += steps
-        self.t.shadows_stale = True
-        return True
-
-    @staticmethod
-    def _covers(s: Tuple[int, int], r: Tuple[int, int]) -> bool:
-        return s[0] <= r[0] and r[0] + r[1] <= s[0] + s[1]
 
     def step_times_ms(self, first: int, last: int) -> np.ndarray:
         """Per-step durations (ms) of global steps [first, last) from the device stamps."""

@@ -3,7 +3,7 @@ mean of back-to-back calls, nothing synchronised in between):
   pybind_noop      a trivial native call (mlpf_stage_rec)
   tiny_launch      a one-block native kernel launch (zero-fill of 16 floats via gemm's zero kernel path)
   plan_launch      PersistF32Plan.launch of a 1-step chunk (the engine's kernel, ~200 B of kernargs)
-  runner_run       PersistentMLPRunner.run(1) (Python fast path + the same launch)
+  runner_run       PersistentMLPRunner.run(1) (the staging planner + the same launch)
 One JSON line."""
 import json
 import os
