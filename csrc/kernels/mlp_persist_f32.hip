@@ -386,12 +386,6 @@ __device__ __forceinline__ void put_gran(__amdgpu_buffer_rsrc_t rs, int voff, f3
     __builtin_amdgcn_raw_buffer_store_b128(hi, rs, voff + 16, 0, 16);
   }
 }
-__device__ __forceinline__ bool get_gran(__amdgpu_buffer_rsrc_t rs, int voff, unsigned tag, f32x4& out) {
-  const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 16);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 16, 0, 16);
-  out = f32x4{__uint_as_float(lo[0]), __uint_as_float(lo[2]), __uint_as_float(hi[0]), __uint_as_float(hi[2])};
-  return lo[1] == tag && lo[3] == tag && hi[1] == tag && hi[3] == tag;
-}
 
 // lane l <- lane l^16 / l^32 with gfx950's VALU row swaps
 __device__ __forceinline__ float xor16(float v) {
@@ -406,10 +400,28 @@ __device__ __forceinline__ float xor32(float v) {
 // Gather the N granule slots slot(k) (k != skip) of this lane until every tag
 // matches; part[skip] = own (constant-index selects only: a runtime index would
 // demote the array to scratch).  `need` false: this lane takes no data (zeros;
-// it still joins the wave-wide exit test).  Every lane loads its own granules
-// directly, pass after pass without sleeping, and re-loads only those that were
-// not there yet (no order between a producer's lanes).  false on timeout / error.
-template <int N, typename SlotOff>
+// it still joins the wave-wide exit test) and loads at an offset past the
+// region's range, which the buffer unit answers with zeros and no traffic.
+//
+// A pass walks the slots in groups of GRP.  A group first issues both 16-byte
+// sc1 loads of every slot that some lane of the wave still lacks (a scalar
+// branch per slot: a slot the whole wave holds costs nothing in later passes),
+// with no wait and no lane mask between the issues, and only then compares
+// tags, so a group costs one L2 round trip plus issue, not one per slot.  A
+// lane takes slot k in the pass in which all four tags of its two loads match,
+// merged into part[k] under !have[k]; part[k] is not touched again (no order
+// between a producer's lanes, so a later pass may see other bytes there).  A
+// slot in flight is 8 VGPRs per lane: GRP bounds them.  Before this, the pass
+// was `if (!have[k]) have[k] = get(...)` per lane, which compiled to one
+// divergent region per slot with a vmcnt(0) in each: N serial round trips
+// (scripts/probes/gather_pass_shape.py reads this off the generated code;
+// tests/test_mlp_persist_gather_shape_cpu.py holds it).  false on timeout / error.
+constexpr int OOB_OFF = 0x7ffffff0;   // a buffer offset past every region's range
+// E2's group size: 7 slots, 6 of them live, as 4 + 3.  6 and 7 leave the resident
+// instrumented instantiation with scratch; 4 measured 0.1 % above 5 and leaves
+// the N-GPU kernels 8 VGPRs more (profiles/mlp_persist_f32_gather_inflight_ab.json)
+constexpr int E2_GRP = 4;
+template <int N, int GRP, typename SlotOff>
 __device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff slot, int skip, bool need, unsigned tag,
                                             f32x4 own, f32x4 (&part)[N], int lane, const Args& a) {
   bool have[N];
@@ -418,19 +430,50 @@ __device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff s
     have[k] = (k == skip) || !need;
     part[k] = (k == skip) ? own : f32x4{0.f, 0.f, 0.f, 0.f};
   }
+  // a lane that takes no data loads past the region's range (zeros, no traffic)
+  const unsigned base = need ? 32u * (unsigned)lane : (unsigned)OOB_OFF;
+  u32x4 lo[GRP] = {}, hi[GRP] = {};   // a group's raw granules: 8 VGPRs per slot in flight
   const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-  asm volatile("" ::: "memory");   // (redundant with the loop's; without it the relu NW = 4 f32-MFMA
-                                   // instantiation gets another register allocation)
-  // the clock and the error word are checked every 8th pass only: a pass is one
-  // L2 round trip, and the consumer CU's memory queue is what a hand-off waits on
+  // the clock and the error word are checked every 8th pass only
   for (int it = 1;; ++it) {
     asm volatile("" ::: "memory");   // re-load every pass (no loop-invariant hoisting)
     bool all = true;
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-      if (!have[k]) have[k] = get_gran(rs, slot(k) + 32 * lane, tag, part[k]);
-      all = all && have[k];
+    for (int g0 = 0; g0 < N; g0 += GRP) {
+      bool go[GRP];
+      // issue: every outstanding slot's two loads, no wait and no lane mask between them
+#pragma unroll
+      for (int i = 0; i < GRP; ++i) {
+        const int k = g0 + i;
+        go[i] = k < N && __any(!have[k < N ? k : 0]);
+        if (go[i]) {
+          const int voff = (int)(base + (unsigned)slot(k));
+          lo[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 16);
+          hi[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 16, 0, 16);
+        }
+      }
+      // the registers as the loads left them, slot by slot, after the last issue:
+      // the compiler neither sinks a load to its use nor regroups the group's
+      // registers into one wide value with copies (and waits) between the issues
+#pragma unroll
+      for (int i = 0; i < GRP; ++i) asm volatile("" : "+v"(lo[i]), "+v"(hi[i]));
+      // accept: all four tags of the lane's two loads match
+#pragma unroll
+      for (int i = 0; i < GRP; ++i) {
+        const int k = g0 + i;
+        if (k < N && go[i]) {
+          const bool hit = lo[i][1] == tag && lo[i][3] == tag && hi[i][1] == tag && hi[i][3] == tag;
+          const bool take = hit && !have[k];
+          const f32x4 v = {__uint_as_float(lo[i][0]), __uint_as_float(lo[i][2]), __uint_as_float(hi[i][0]),
+                           __uint_as_float(hi[i][2])};
+#pragma unroll
+          for (int c = 0; c < 4; ++c) part[k][c] = take ? v[c] : part[k][c];
+          have[k] = have[k] || hit;
+        }
+      }
     }
+#pragma unroll
+    for (int k = 0; k < N; ++k) all = all && have[k];
     if (__all(all)) return true;
     if ((it & 7) == 0 && ((long long)__builtin_amdgcn_s_memrealtime() - t0 > a.timeout ||
                           __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
@@ -449,7 +492,6 @@ __device__ __forceinline__ bool gather_gran(__amdgpu_buffer_rsrc_t rs, SlotOff s
 // (no branch, no wait between them: all in flight at once) and only payload
 // crosses the fabric.
 constexpr int SYS = 1 | 16;            // sc0 | sc1
-constexpr int OOB_OFF = 0x7ffffff0;
 // one resource per rank, built once per launch in SGPRs (the table entry is read
 // by one lane and broadcast: a per-use vector load of the pointer would turn
 // every peer load into a waterfall loop behind a vmcnt(0))
@@ -1244,7 +1286,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
         b2v[e] = b2s[4 * g + e];
       }
       f32x4 part[NQ];
-      bool ok = gather_gran<NQ>(r1, [&](int k) { return (k * NBT + w) * GSLOT; }, jq[1], true, tag, zs, part, lane, a);
+      bool ok = gather_gran<NQ, NQ>(r1, [&](int k) { return (k * NBT + w) * GSLOT; }, jq[1], true, tag, zs, part, lane, a);
       f32x4 z = part[0];
 #pragma unroll
       for (int qq = 1; qq < NQ; ++qq) z += part[qq];
@@ -1273,7 +1315,7 @@ __device__ void compute(const Args& a, const int j, const int q, uint8_t* smem) 
 #pragma unroll
       for (int i = 0; i < 4; ++i) a2T[(4 * g + i) * LS + bw] = a2[i];
       f32x4 lp[NJ];
-      ok = gather_gran<NJ>(r2, [&](int k) { return k * GSLOT; }, jq[0], g < 3, tag, pl, lp, lane, a) && ok;
+      ok = gather_gran<NJ, E2_GRP>(r2, [&](int k) { return k * GSLOT; }, jq[0], g < 3, tag, pl, lp, lane, a) && ok;
       if (w == 0) { PH(7); }
       if (!ok && lane == 0) *abort_flag = 1;
       // logits and softmax -- identical in every workgroup.  Only what dz3 needs
