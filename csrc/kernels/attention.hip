@@ -1,6 +1,7 @@
 // Reached by: models/bert.py (BERT-base: bench_models.py --model bert_base); tests/test_transformer_gpu.py
 // Fused multi-head self-attention for BERT-shaped layers (head dim 64,
-// S <= 256, S % 32 == 0) on CDNA4 MFMA -- forward and backward.
+// S <= 256, S % 32 == 0; longer sequences: attention_long.hip) on CDNA4 MFMA --
+// forward and backward.
 //
 // The unfused path is QK^T (batched GEMM) -> masked softmax + dropout ->
 // PV (batched GEMM), plus permute copies of q/k/v/ctx in both directions,
@@ -31,7 +32,13 @@
 // Dropout keep(i) = hash32(seed, i) >= p * 2^32 with i the element index of
 // the [B, NH, S, S] probability tensor -- the same convention as the unfused
 // softmax kernel (transformer.hip), so both paths drop the same elements.
+//
+// S = 384 ... 2048 (multiples of 128) is attention_long.hip: the same orientation
+// with key / query blocks streamed through LDS and a running softmax.  The entry
+// points below stay the only ones the binding calls and pass S > 256 on; the
+// helpers both files use are in attention_device.h.
 #include "common.h"
+#include "attention_device.h"
 #include "transformer_api.h"
 
 #include <cstdlib>
@@ -39,53 +46,6 @@
 
 namespace dtfk {
 namespace attn {
-
-constexpr int D = 64;
-constexpr int KP = 72;     // padded row of a [S][64] LDS image (144 B: rows spread over banks)
-
-__device__ __forceinline__ uint4 add_bias8(uint4 u, const float* __restrict__ bias) {
-  if (!bias) return u;
-  const float4 b0 = *reinterpret_cast<const float4*>(bias);
-  const float4 b1 = *reinterpret_cast<const float4*>(bias + 4);
-  const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-  uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w[j] = pack2bf(bf2f(w[j] & 0xffff) + bb[2 * j], bf2f(w[j] >> 16) + bb[2 * j + 1]);
-  return uint4{w[0], w[1], w[2], w[3]};
-}
-
-__device__ __forceinline__ uint4 ld16(const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); }
-
-__device__ __forceinline__ bf16x8 as_frag(uint4 u) { return __builtin_bit_cast(bf16x8, u); }
-
-// The permuted 32-key fragment of a TRANSPOSED operand straight from a
-// row-major [S][KP] image with the gfx950 transposed LDS read
-// (ds_read_b64_tr_b16: per 16-lane group, lane 4q+p addresses row q, columns
-// 4p..4p+3 of a 4 x 16 block; lane i receives column i): lane (g, c) gets
-// column col0 + c of rows row0 + 4g + 0..3 (elements 0..3) and row0 + 16 + 4g +
-// 0..3 (elements 4..7) -- the k-slot order of the score accumulators.  Replaces
-// a second, transposed LDS image written with 2-byte scatter stores.  EXEC must
-// be full (wave-uniform control flow only).
-typedef __attribute__((ext_vector_type(4))) short v4s_t;
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-__device__ __forceinline__ bf16x8 ld_tr_pair(const uint16_t* img, int row0, int col0, int l) {
-  const int g = l >> 4, q = (l >> 2) & 3, p = l & 3;
-  const uint16_t* a = img + (row0 + 4 * g + q) * KP + col0 + 4 * p;
-  const v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(a));
-  const v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(a + 16 * KP));
-  typedef __attribute__((ext_vector_type(8))) short v8s_t;
-  const v8s_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ bf16x8 pack8(const float* f) {
-  return as_frag(uint4{pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7])});
-}
-
-__device__ __forceinline__ float keepf(uint64_t seed, uint64_t i, uint32_t thresh, float inv_keep) {
-  return (thresh == 0u) ? 1.f : (hash32(seed, i) >= thresh ? inv_keep : 0.f);
-}
 
 // stage a [S][64] tile (rows of the packed projection, or of a [B,S,NH*64]
 // tensor) into a row image rows[S][KP] (the products that need it transposed
@@ -673,12 +633,6 @@ __global__ __launch_bounds__(512) void attn_bwd_fused(const uint16_t* __restrict
 
 using namespace dtfk::attn;
 
-static inline uint32_t attn_thresh(float p) {
-  if (p <= 0.f) return 0u;
-  double t = (double)p * 4294967296.0;
-  return t >= 4294967295.0 ? 4294967295u : (uint32_t)t;
-}
-
 // >64 KB dynamic LDS must be opted into once per kernel instantiation
 template <typename K>
 static hipError_t allow_lds(K kern, size_t lds) {
@@ -688,9 +642,20 @@ static hipError_t allow_lds(K kern, size_t lds) {
 
 extern "C" {
 
+// S = 384 ... 2048 in steps of 128: the streamed kernels of attention_long.hip,
+// unless DTF_ATTN_LONG=0 (read once per process) refuses them as before
+static bool attn_long_ok(int S) {
+  static const bool on = [] {
+    const char* e = std::getenv("DTF_ATTN_LONG");
+    return e == nullptr || std::string(e) != "0";
+  }();
+  return on && S % 128 == 0 && S >= 384 && S <= 2048;
+}
+
 int dtfk_attn_supported(int S, int d) {
   const int n = S / 32;
-  return d == D && S % 32 == 0 && (n == 1 || n == 2 || n == 4 || n == 6 || n == 8);
+  if (d != D) return 0;
+  return (S % 32 == 0 && (n == 1 || n == 2 || n == 4 || n == 6 || n == 8)) || attn_long_ok(S);
 }
 
 #define DTFK_ATTN_DISPATCH(S, MACRO) \
@@ -706,6 +671,7 @@ int dtfk_attn_supported(int S, int d) {
 hipError_t dtfk_attn_fwd(const void* qkv, const float* bias, const float* mask, void* ctx, float* lse, int B, int S,
                          int NH, float scale, float p, unsigned long long seed, hipStream_t st) {
   if (!dtfk_attn_supported(S, D)) return hipErrorInvalidValue;
+  if (S > 256) return dtfk_attn_long_fwd(qkv, bias, mask, ctx, lse, B, S, NH, scale, p, seed, st);
   const dim3 grid((S + 127) / 128, NH, B);
   const float ik = p > 0.f ? 1.f / (1.f - p) : 1.f;
   const size_t lds = (size_t)(2 * S * KP) * 2;
@@ -728,6 +694,8 @@ hipError_t dtfk_attn_bwd(const void* qkv, const float* bias, const float* mask, 
   // bpart (optional): [B * S / 16, 3 * NH * 64] fp32 partial column sums of dqkv
   // (the qkv bias gradient before its colsum_partials reduction)
   if (!dtfk_attn_supported(S, D)) return hipErrorInvalidValue;
+  if (S > 256)
+    return dtfk_attn_long_bwd(qkv, bias, mask, ctx, dctx, lse, Dbuf, dqkv, B, S, NH, scale, p, seed, bpart, st);
   const dim3 grid((S + 127) / 128, NH, B);
   const float ik = p > 0.f ? 1.f / (1.f - p) : 1.f;
   const uint32_t th = attn_thresh(p);

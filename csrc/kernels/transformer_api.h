@@ -52,4 +52,11 @@ hipError_t dtfk_attn_bwd(const void* qkv, const float* bias, const float* mask, 
                          const float* lse, float* Dbuf, void* dqkv, int B, int S, int NH, float scale, float p,
                          unsigned long long seed, float* bpart, hipStream_t st);
 
+// ---- attention_long.hip: S = 384 ... 2048, S % 128 == 0, same arguments; reached through the two above
+hipError_t dtfk_attn_long_fwd(const void* qkv, const float* bias, const float* mask, void* ctx, float* lse, int B,
+                              int S, int NH, float scale, float p, unsigned long long seed, hipStream_t st);
+hipError_t dtfk_attn_long_bwd(const void* qkv, const float* bias, const float* mask, const void* ctx,
+                              const void* dctx, const float* lse, float* Dbuf, void* dqkv, int B, int S, int NH,
+                              float scale, float p, unsigned long long seed, float* bpart, hipStream_t st);
+
 }  // extern "C"

@@ -45,7 +45,7 @@ class BertConfig:
     attn_dropout: float = 0.1
     ln_eps: float = 1e-12
     init_std: float = 0.02
-    fused_attention: bool = True    # GPU: attention.hip straight from the packed QKV projection
+    fused_attention: bool = True    # GPU: attention.hip / attention_long.hip straight from the packed QKV projection
 
     @staticmethod
     def base():
@@ -283,7 +283,7 @@ class BertLayer(torch.nn.Module):
         nh, d = c.heads, H // c.heads
         slot_x = _slot_for(x, self.w_qkv)      # LN1's residual grad of x -> QKV GEMM's dX
         if x.is_cuda and c.fused_attention and T.attention_supported(S, d):
-            # q/k/v read in place from the packed projection, bias fused (attention.hip)
+            # q/k/v read in place from the packed projection, bias fused (attention.hip; S >= 384: attention_long.hip)
             ctx = T.fused_attention(_mm(x, self.w_qkv, slot_x), self.b_qkv, mask, nh, 1.0 / math.sqrt(d),
                                     c.attn_dropout, self.training)
         else:

@@ -476,7 +476,9 @@ def fused_attention(qkv, bias, mask: Optional[torch.Tensor], nh: int, scale: flo
     qkv [B, S, 3*nh*64] (pre-bias GEMM output, bf16 on GPU), bias [3*nh*64]
     fp32 or None, mask [B, S] additive fp32 or None -> context [B, S, nh*64].
     GPU: csrc/kernels/attention.hip (one pass forward, two backward; prob
-    dropout regenerated from its hash).  CPU: attention_reference."""
+    dropout regenerated from its hash) at S <= 256, attention_long.hip (streamed
+    key blocks, running softmax) at S = 384 ... 2048 in steps of 128; see
+    attention_supported.  CPU: attention_reference."""
     p = p if training else 0.0
     if not qkv.is_cuda:
         return attention_reference(qkv, bias, mask, nh, scale, p)
