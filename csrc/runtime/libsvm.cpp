@@ -16,6 +16,8 @@
 #include <condition_variable>
 
 #include "cv_wait.h"
+#include "libsvm_host.h"
+#include "../kernels/libsvm_rule.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,21 +31,6 @@
 
 namespace dtf {
 namespace libsvm {
-
-struct CSR {
-  std::vector<float> labels;
-  std::vector<int64_t> row_ptr{0};
-  std::vector<int64_t> ids;
-  std::vector<float> vals;
-  int64_t rows() const { return (int64_t)labels.size(); }
-  void append(const CSR& o) {
-    const int64_t base = (int64_t)ids.size();
-    labels.insert(labels.end(), o.labels.begin(), o.labels.end());
-    for (size_t i = 1; i < o.row_ptr.size(); ++i) row_ptr.push_back(base + o.row_ptr[i]);
-    ids.insert(ids.end(), o.ids.begin(), o.ids.end());
-    vals.insert(vals.end(), o.vals.begin(), o.vals.end());
-  }
-};
 
 struct Rng {  // xorshift64*
   uint64_t s;
@@ -109,6 +96,38 @@ static void parse_buffer(const char* data, size_t n, double rate, Rng& rng, CSR&
   }
 }
 
+// parse_buffer's sibling for the GPU parser's fallback and its rate < 1 sample: the same
+// pieces, the same parse_line, but line `ordinal` is kept by lsv::keep (a hash of the
+// ordinal: evaluable per line in parallel) instead of the sequential xorshift draw, so at
+// rate < 1 it keeps another, equally distributed, deterministic sample.  At rate 1 both
+// keep every line and this is parse_buffer.
+int64_t parse_buffer_hashed(const char* data, size_t n, double rate, uint64_t seed, int64_t first_ordinal, CSR& out,
+                            int64_t* bad_lines) {
+  const char* p = data;
+  const char* end = data + n;
+  int64_t pieces = 0;
+  if (rate >= 1.0) {
+    Rng rng(seed);
+    parse_buffer(data, n, 1.0, rng, out, bad_lines);
+    while (p < end) {
+      const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+      ++pieces;
+      p = nl ? nl + 1 : end;
+    }
+    return pieces;
+  }
+  while (p < end) {
+    const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+    const char* le = nl ? nl : end;
+    if (le - p >= 2 && lsv::keep(seed, (uint64_t)(first_ordinal + pieces), rate)) {
+      if (!parse_line(p, le, out) && bad_lines) ++*bad_lines;
+    }
+    ++pieces;
+    p = nl ? nl + 1 : end;
+  }
+  return pieces;
+}
+
 static std::string read_file(const std::string& path) {
   FILE* f = fopen(path.c_str(), "rb");
   if (!f) throw std::runtime_error("cannot open " + path);
@@ -144,6 +163,23 @@ py::tuple parse_bytes(py::bytes data, double rate, uint64_t seed) {
     parse_buffer(s.data(), s.size() - 1, rate, rng, out, &bad);
   }
   return to_py(std::move(out));
+}
+
+// libsvm_parse_bytes with the hashed sample (parse_buffer_hashed): (labels, row_ptr, ids,
+// vals, pieces, bad_lines)
+py::tuple parse_bytes_hashed(py::bytes data, double rate, uint64_t seed, int64_t first_ordinal) {
+  if (!(rate > 0.0 && rate <= 1.0)) throw std::invalid_argument("sampling_rate must be in (0, 1]");
+  if (first_ordinal < 0) throw std::invalid_argument("first_ordinal must not be negative");
+  std::string s = data;
+  s.push_back('\0');
+  CSR out;
+  int64_t bad = 0, pieces = 0;
+  {
+    py::gil_scoped_release nogil;
+    pieces = parse_buffer_hashed(s.data(), s.size() - 1, rate, seed, first_ordinal, out, &bad);
+  }
+  return py::make_tuple(to_np(std::move(out.labels)), to_np(std::move(out.row_ptr)), to_np(std::move(out.ids)),
+                        to_np(std::move(out.vals)), pieces, bad);
 }
 
 // thread t parses files[t::nthreads] (reference InitThreads striding); the
@@ -299,6 +335,8 @@ void init_libsvm(py::module& m) {
   using namespace libsvm;
   m.def("libsvm_parse_bytes", &parse_bytes, py::arg("data"), py::arg("sampling_rate") = 1.0,
         py::arg("seed") = 0);
+  m.def("libsvm_parse_bytes_hashed", &parse_bytes_hashed, py::arg("data"), py::arg("sampling_rate") = 1.0,
+        py::arg("seed") = 0, py::arg("first_ordinal") = 0);
   m.def("libsvm_parse_files", &parse_files, py::arg("files"), py::arg("nthreads") = 2,
         py::arg("sampling_rate") = 1.0, py::arg("seed") = 0);
   py::class_<Stream>(m, "LibsvmStream")

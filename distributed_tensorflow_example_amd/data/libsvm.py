@@ -16,10 +16,21 @@ reference is derivable (`CSRBatch.coo_indices`).  'queue' mode is the native
 `LibsvmStream` (bounded queue of ready CSR batches, looping over the files).
 Intentional fix: the reference's queue-mode test sampler reads the *train*
 queue (lr2.py:213-217, "should be 'test'"); here it reads the test stream.
+
+`parser="gpu"` (opt-in; the default stays "cpu") parses the text on the GPU
+instead (csrc/kernels/libsvm_parse.hip): file bytes go through pinned buffers to
+the device and come out as `DeviceCSR` -- device CSR already cut into batches,
+each a zero-copy view -- which the sparse trainers take as they take a
+`CSRBatch.to(device)` tuple.  At sampling rate 1 both parsers give the same
+bits (a chunk the GPU's strict grammar does not cover is parsed by the C++
+parser instead); at a rate below 1 the GPU path keeps another sample: see
+`GpuLibsvmParser`.
 """
 from __future__ import annotations
 
 import os
+import queue
+import threading
 import time
 from dataclasses import dataclass
 from typing import Iterator, List, Optional, Sequence
@@ -107,8 +118,17 @@ def parse_lines(lines: Sequence[str], sampling_rate: float = 1.0, seed: int = 0)
     return CSRData(y, rp, ids, vals)
 
 
-def load_files(files: Sequence[str], nthreads: int = 2, sampling_rate: float = 1.0, seed: int = 0) -> CSRData:
-    """Parse files (local, file:// or hdfs://) with `nthreads` native threads."""
+def load_files(files: Sequence[str], nthreads: int = 2, sampling_rate: float = 1.0, seed: int = 0,
+               parser: str = "cpu", device=None) -> CSRData:
+    """Parse files (local, file:// or hdfs://) with `nthreads` native threads, or,
+    with parser="gpu", on `device` (default: the current GPU) in file order and
+    bring the result back to the host.  The GPU result equals the nthreads=1 CPU
+    result at sampling_rate 1; below 1 it is the hashed sample (GpuLibsvmParser)."""
+    if parser not in ("cpu", "gpu"):
+        raise ValueError("parser must be 'cpu' or 'gpu'")
+    if parser == "gpu":
+        gp = GpuLibsvmParser(device=device, sampling_rate=sampling_rate, seed=seed)
+        return CSRData.concat([d.to_host() for d in gp.parse_files(files)])
     C = _native.load()
     local = [gfile.local_path(f) for f in files]
     if all(p is not None for p in local):
@@ -120,6 +140,259 @@ def load_files(files: Sequence[str], nthreads: int = 2, sampling_rate: float = 1
             y, rp, ids, vals = C.libsvm_parse_bytes(fh.read(), float(sampling_rate), int(seed) + i)
         parts.append(CSRData(y, rp, ids, vals))
     return CSRData.concat(parts)
+
+
+class DeviceCSR:
+    """One parsed chunk on the GPU, cut into batches of `batch_size` rows.
+
+    labels [R] f32, ids / vals [nnz], offsets [batches, batch_size + 1] i64 with
+    every row rebased on its batch's first entry, bases (host int64
+    [batches + 1]) into ids / vals: batch b is views of the four, no copy.
+    `carry_rows` > 0 (a stream's chunk): the first batch is short by that many
+    rows -- it completes rows carried over from the chunk before -- and its
+    offsets continue from `carry_nnz`."""
+
+    def __init__(self, labels, offsets, ids, vals, bases, batch_size, carry_rows=0, carry_nnz=0, lines=0,
+                 irregular=False, bad_lines=0):
+        self.labels, self.offsets, self.ids, self.vals = labels, offsets, ids, vals
+        self.bases = np.asarray(bases, np.int64)
+        self.batch_size, self.carry_rows, self.carry_nnz = int(batch_size), int(carry_rows), int(carry_nnz)
+        self.lines, self.irregular, self.bad_lines = int(lines), bool(irregular), int(bad_lines)
+
+    def __len__(self):
+        return int(self.labels.shape[0])
+
+    @property
+    def nnz(self) -> int:
+        return int(self.ids.shape[0])
+
+    @property
+    def num_batches(self) -> int:
+        return int(self.offsets.shape[0])
+
+    def _span(self, b):
+        """(first row, end row, first offsets column) of batch b."""
+        bs, c, R = self.batch_size, self.carry_rows, len(self)
+        return max(b * bs - c, 0), min((b + 1) * bs - c, R), (c if b == 0 else 0)
+
+    def batch(self, b):
+        r0, r1, j0 = self._span(b)
+        s, e = int(self.bases[b]), int(self.bases[b + 1])
+        return (self.labels[r0:r1].view(-1, 1), self.offsets[b, j0:j0 + (r1 - r0) + 1], self.ids[s:e], self.vals[s:e])
+
+    def batches(self):
+        """(labels [B,1], offsets [B+1], ids, vals) device views, batch by batch."""
+        for b in range(self.num_batches):
+            yield self.batch(b)
+
+    def to_host(self) -> CSRData:
+        off = self.offsets.cpu().numpy()
+        parts = [np.zeros(1, np.int64)]
+        for b in range(self.num_batches):
+            r0, r1, j0 = self._span(b)
+            parts.append(off[b, j0 + 1:j0 + 1 + (r1 - r0)] - off[b, j0] + self.bases[b])
+        return CSRData(self.labels.cpu().numpy(), np.concatenate(parts), self.ids.cpu().numpy(),
+                       self.vals.cpu().numpy())
+
+
+def _after_last_newline(buf: np.ndarray, n: int) -> int:
+    """One past the last '\\n' of buf[:n], 0 when there is none (searched from the end, 64 KB at a time)."""
+    e = n
+    while e > 0:
+        s = max(0, e - 65536)
+        hit = np.flatnonzero(buf[s:e] == 10)
+        if hit.size:
+            return s + int(hit[-1]) + 1
+        e = s
+    return 0
+
+
+class GpuLibsvmParser:
+    """libsvm text -> `DeviceCSR` with the HIP parser (native `LibsvmGpuParser`).
+
+    The kernels accept a strict grammar and compute every number so that it
+    equals strtof's; a chunk holding anything else (inf, nan, hex floats, signed
+    or very long indices, stray bytes, numbers of more than 15 digits or on a
+    float32 tie, ...) is parsed by the C++ parser instead and uploaded
+    (`fallback_chunks`, `bad_lines`).  So at sampling_rate 1 the result is the
+    C++ parser's, bit for bit.  At sampling_rate < 1 the C++ parser draws from a
+    sequential xorshift per line, which cannot be evaluated in parallel: this
+    parser keeps line `ordinal` -- a running count of the '\\n'-separated pieces
+    of the call or the stream -- iff a hash of (seed, ordinal) is below the
+    rate: a different, equally distributed, deterministic sample
+    (`libsvm_parse_bytes_hashed` is its host form)."""
+
+    def __init__(self, device=None, chunk_bytes: int = 16 << 20, batch_size: int = 500, sampling_rate: float = 1.0,
+                 seed: int = 0):
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("GpuLibsvmParser needs a GPU device")
+        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self.chunk_bytes, self.batch_size = int(chunk_bytes), int(batch_size)
+        self._p = _native.load().LibsvmGpuParser(self.device.index, self.chunk_bytes, self.batch_size,
+                                                 float(sampling_rate), int(seed))
+        self._stage = [self._p.staging(0).numpy(), self._p.staging(1).numpy()]
+
+    gpu_chunks = property(lambda self: self._p.gpu_chunks)
+    fallback_chunks = property(lambda self: self._p.fallback_chunks)
+    bad_lines = property(lambda self: self._p.bad_lines)
+
+    def _wrap(self, res, carry_rows, carry_nnz):
+        labels, offsets, ids, vals, bases, _rows, _nnz, lines, irregular, bad = res
+        return DeviceCSR(labels, offsets, ids, vals, bases.numpy(), self.batch_size, carry_rows, carry_nnz, lines,
+                         irregular, bad)
+
+    def parse_bytes(self, data: bytes, first_ordinal: int = 0) -> DeviceCSR:
+        """One chunk (at most chunk_bytes) of text."""
+        return self._wrap(self._p.parse(bytes(data), int(first_ordinal), 0, 0, 0), 0, 0)
+
+    def parse_slot(self, slot: int, nbytes: int, first_ordinal: int = 0, carry_rows: int = 0,
+                   carry_nnz: int = 0) -> DeviceCSR:
+        """The first `nbytes` of pinned staging buffer `slot` (filled in place by a reader)."""
+        return self._wrap(self._p.parse(int(slot), int(first_ordinal), int(nbytes), int(carry_rows), int(carry_nnz)),
+                          carry_rows, carry_nnz)
+
+    def fill_chunks(self, files: Sequence[str], loop: bool, take_slot, stopped=lambda: False):
+        """Reads `files` in order into the pinned buffers and yields (slot, nbytes) per
+        chunk: a chunk is cut at its last newline and the tail moves to the front of the
+        next buffer; a file's end closes a chunk.  `take_slot()` hands out the next free
+        buffer.  A line longer than chunk_bytes raises ValueError naming the file."""
+        cap = self.chunk_bytes
+        while not stopped():
+            for f in files:
+                path = gfile.local_path(f)
+                fh = open(path, "rb", buffering=0) if path is not None else gfile.GFile(f, "rb")
+                with fh:
+                    tail = b""
+                    eof = False
+                    while not eof and not stopped():
+                        slot = take_slot()
+                        if slot is None:
+                            return
+                        buf = self._stage[slot]
+                        n = len(tail)
+                        buf[:n] = np.frombuffer(tail, np.uint8)
+                        while n < cap:
+                            if hasattr(fh, "readinto"):
+                                k = fh.readinto(memoryview(buf)[n:cap])
+                            else:
+                                got = fh.read(cap - n)
+                                k = len(got)
+                                buf[n:n + k] = np.frombuffer(got, np.uint8)
+                            if not k:
+                                eof = True
+                                break
+                            n += k
+                        tail = b""
+                        if not eof:
+                            cut = _after_last_newline(buf, n)
+                            if cut == 0:
+                                more = fh.read(1)
+                                if more:
+                                    raise ValueError(f"{f}: a line is longer than chunk_bytes = {cap}")
+                                eof = True
+                            else:
+                                tail = buf[cut:n].tobytes()
+                                n = cut
+                        if n:
+                            yield slot, n
+            if not loop or not files:
+                return
+
+    def parse_files(self, files: Sequence[str]):
+        """`DeviceCSR` chunks of the files in order; the ordinal runs over all of them."""
+        out, ordinal, slot = [], 0, [1]
+
+        def take():
+            slot[0] ^= 1
+            return slot[0]
+
+        for s, n in self.fill_chunks(files, False, take):
+            d = self.parse_slot(s, n, ordinal)
+            ordinal += d.lines
+            out.append(d)
+        return out
+
+
+class GpuBatchStream:
+    """queue mode on the GPU parser: one reader thread fills the two pinned buffers
+    while the consumer parses the other one; iterating yields device batches of
+    exactly batch_size rows (rows left after a chunk's last whole batch are
+    carried, on the device, into the next chunk's first batch); only the last
+    batch of a non-looping stream may be short."""
+
+    def __init__(self, parser: GpuLibsvmParser, files: Sequence[str], loop: bool = False):
+        self.parser, self.files, self.loop = parser, list(files), loop
+        self._free, self._full = queue.Queue(), queue.Queue()
+        self._free.put(0)
+        self._free.put(1)
+        self._stop = threading.Event()
+        self._thread = threading.Thread(target=self._read, daemon=True)
+        self._thread.start()
+        self._it = self._batches()
+        self.rows_emitted = 0
+
+    def _take(self):
+        while not self._stop.is_set():
+            try:
+                return self._free.get(timeout=0.05)
+            except queue.Empty:
+                continue
+        return None
+
+    def _read(self):
+        try:
+            for item in self.parser.fill_chunks(self.files, self.loop, self._take, self._stop.is_set):
+                self._full.put(item)
+            self._full.put(None)
+        except BaseException as e:  # noqa: BLE001 (handed to the consumer)
+            self._full.put(e)
+
+    def _batches(self):
+        import torch
+
+        bs = self.parser.batch_size
+        carry, c, cnnz, ordinal = None, 0, 0, 0
+        while True:
+            item = self._full.get()
+            if item is None:
+                break
+            if isinstance(item, BaseException):
+                raise item
+            slot, n = item
+            d = self.parser.parse_slot(slot, n, ordinal, c, cnnz)
+            self._free.put(slot)                 # parse() returned: the buffer is consumed
+            ordinal += d.lines
+            for b in range(d.num_batches):
+                y, off, ids, vals = d.batch(b)
+                if b == 0 and c:
+                    y = torch.cat([carry[0], y])
+                    off = torch.cat([carry[1][:c], off])
+                    ids, vals = torch.cat([carry[2], ids]), torch.cat([carry[3], vals])
+                if y.shape[0] == bs:
+                    carry, c, cnnz = None, 0, 0
+                    self.rows_emitted += bs
+                    yield y, off, ids, vals
+                else:                            # the chunk's last, short batch: carried
+                    carry, c, cnnz = (y, off, ids, vals), int(y.shape[0]), int(ids.shape[0])
+        if c:
+            self.rows_emitted += c
+            yield carry
+
+    def next(self):
+        """The next batch, or None at the end of a non-looping stream."""
+        return next(self._it, None)
+
+    def stop(self):
+        self._stop.set()
+        while self._thread.is_alive():
+            try:                                  # a reader blocked on a full hand-off
+                self._full.get_nowait()
+            except queue.Empty:
+                pass
+            self._thread.join(0.05)
 
 
 def split_file_list(spec: str, num_workers: int = 1, task_index: int = 0) -> List[str]:
@@ -144,9 +417,19 @@ class DataProvider:
 
     def __init__(self, num_workers: int, task_index: int, thread_num: int = 2, mode: str = "all",
                  train: str = "", test: str = "", batch_size: int = 500, train_sampling_rate: float = 1.0,
-                 test_sampling_rate: float = 1.0, queue_capacity: int = 16, seed: int = 0):
+                 test_sampling_rate: float = 1.0, queue_capacity: int = 16, seed: int = 0, parser: str = "cpu",
+                 device=None, chunk_bytes: int = 16 << 20):
+        """`parser="gpu"`: the files are parsed on `device` (GpuLibsvmParser).  'all' mode
+        brings the result back as CSRData, so shuffling and `take` stay as they are;
+        'queue' mode's NextBatch yields device tuples (labels, offsets, ids, vals) of
+        exactly batch_size rows, in file order, which train_step / evaluate /
+        auc_update / evaluate_stream accept as they are."""
         if mode not in ("all", "queue"):
             raise ValueError("mode must be 'all' or 'queue'")
+        if parser not in ("cpu", "gpu"):
+            raise ValueError("parser must be 'cpu' or 'gpu'")
+        self.parser, self.device, self.chunk_bytes = parser, device, int(chunk_bytes)
+        self._gpu_parsers = {}
         self.mode, self.num_workers, self.task_index = mode, num_workers, task_index
         self.thread_num = max(1, int(thread_num))
         self.batch_size = int(batch_size)
@@ -173,8 +456,15 @@ class DataProvider:
     def LoadData(self):  # noqa: N802 (reference name)
         t0 = time.time()
         if self.mode == "all":
-            self.train = load_files(self.train_file_list, self.thread_num, self.train_rate, self.seed)
-            self.test = load_files(self.test_file_list, self.thread_num, self.test_rate, self.seed + 7919)
+            if self.parser == "gpu":
+                for kind, files, rate, seed in (("train", self.train_file_list, self.train_rate, self.seed),
+                                                ("test", self.test_file_list, self.test_rate, self.seed + 7919)):
+                    gp = self._gpu_parsers[kind] = GpuLibsvmParser(self.device, self.chunk_bytes, self.batch_size,
+                                                                   float(rate), int(seed))
+                    setattr(self, kind, CSRData.concat([d.to_host() for d in gp.parse_files(files)]))
+            else:
+                self.train = load_files(self.train_file_list, self.thread_num, self.train_rate, self.seed)
+                self.test = load_files(self.test_file_list, self.thread_num, self.test_rate, self.seed + 7919)
             self._order = np.arange(len(self.train))
             log.info(f"[worker:{self.task_index}] loaded {len(self.train)} train / {len(self.test)} test "
                      f"samples from {len(self.train_file_list)}+{len(self.test_file_list)} files "
@@ -184,7 +474,11 @@ class DataProvider:
             for kind, files, rate in (("train", self.train_file_list, self.train_rate),
                                       ("test", self.test_file_list, self.test_rate)):
                 local = [gfile.local_path(f) or f for f in files]
-                if files:
+                if files and self.parser == "gpu":
+                    gp = GpuLibsvmParser(self.device, self.chunk_bytes, self.batch_size, float(rate), int(self.seed))
+                    self._gpu_parsers[kind] = gp
+                    self._streams[kind] = GpuBatchStream(gp, files, loop=True)
+                elif files:
                     self._streams[kind] = C.LibsvmStream(local, self.batch_size, self.thread_num, float(rate),
                                                          True, int(self.queue_capacity), int(self.seed))
         return self
@@ -193,6 +487,12 @@ class DataProvider:
         for s in self._streams.values():
             s.stop()
         self._streams.clear()
+
+    def parser_stats(self) -> dict:
+        """gpu_chunks / fallback_chunks / bad_lines summed over this provider's GPU parsers."""
+        ps = self._gpu_parsers.values()
+        return {"gpu_chunks": sum(p.gpu_chunks for p in ps), "fallback_chunks": sum(p.fallback_chunks for p in ps),
+                "bad_lines": sum(p.bad_lines for p in ps)}
 
     # ------------------------------------------------------------ accessors
     def GetTrainSamples(self) -> CSRData:  # noqa: N802
@@ -220,9 +520,13 @@ class DataProvider:
                 return
             k = 0
             while max_batches is None or k < max_batches:
-                b = st.next(30.0)
+                b = st.next() if self.parser == "gpu" else st.next(30.0)
                 if b is None:
                     return
+                if self.parser == "gpu":
+                    yield b
+                    k += 1
+                    continue
                 y, rp, ids, vals = b
                 yield CSRBatch(np.asarray(y, np.float32).reshape(-1, 1), rp, ids, vals)
                 k += 1
@@ -235,6 +539,8 @@ class DataProvider:
             return self.test.take(np.sort(rows))
         parts = []
         for b in self.NextBatch("test", max_batches=max(1, sampling_max_num // self.batch_size)):
+            if isinstance(b, tuple):             # parser="gpu": device tensors
+                b = CSRBatch(*(t.cpu().numpy() for t in b))
             parts.append(CSRData(b.labels, b.offsets, b.ids, b.vals))
         d = CSRData.concat(parts)
         return d.slice(0, len(d))

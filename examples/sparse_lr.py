@@ -18,7 +18,11 @@ Same flags and console lines as the reference (lr2.py:19-35, :307-315,
   declares the flag);
 * `--optimizer=ftrl` trains with tf.train.FtrlOptimizer's rule (`--l1`, `--l2`,
   `--learning_rate_power`): the result JSON then reports `zero_share`, the
-  share of exactly-zero weights among the rows the training touched.
+  share of exactly-zero weights among the rows the training touched;
+* `--parser=gpu` parses the libsvm text on the GPU (HIP kernels, data/libsvm.py
+  GpuLibsvmParser) instead of the C++ threads; in queue mode the batches then stay
+  on the device.  The default is `cpu`.  The result JSON reports `parser`,
+  `gpu_chunks` and `fallback_chunks` (chunks the GPU handed back to the C++ parser).
 """
 from __future__ import annotations
 
@@ -66,6 +70,8 @@ flags.DEFINE_string("optimizer", "sgd", "sgd (lr2.py's GradientDescentOptimizer)
 flags.DEFINE_float("l1", 0.0, "ftrl: l1_regularization_strength")
 flags.DEFINE_float("l2", 0.0, "ftrl: l2_regularization_strength")
 flags.DEFINE_float("learning_rate_power", -0.5, "ftrl: learning_rate_power (<= 0)")
+flags.DEFINE_string("parser", "cpu", "libsvm parser: cpu (C++ threads) or gpu (HIP kernels)")
+flags.DEFINE_integer("chunk_bytes", 16 << 20, "parser=gpu: text bytes per parsed chunk")
 FLAGS = flags.FLAGS
 
 
@@ -88,7 +94,8 @@ def main(_argv):
                              train_sampling_rate=FLAGS.train_sampling_rate,
                              test_sampling_rate=FLAGS.test_sampling_rate,
                              queue_capacity=max(2, FLAGS.train_queue_capacity // FLAGS.batch_size),
-                             seed=FLAGS.seed).init()
+                             seed=FLAGS.seed, parser=FLAGS.parser, device=world.device if FLAGS.parser == "gpu" else None,
+                             chunk_bytes=FLAGS.chunk_bytes).init()
     log.info("load data")
     dp.LoadData()
     log.info("build model")
@@ -147,7 +154,9 @@ def main(_argv):
     result = {"auc": auc, "loss": last_loss, "global_step": model.global_step,
               "b": float(model.b.detach().cpu()[0]), "steps": step, "train_s": train_s,
               # evaluations that ran on the fused one-GPU plan (forward-only kernels)
-              "fused_evals": model.fused_eval_runs()}
+              "fused_evals": model.fused_eval_runs(), "parser": FLAGS.parser}
+    stats = dp.parser_stats()
+    result.update(gpu_chunks=stats["gpu_chunks"], fallback_chunks=stats["fallback_chunks"])
     if FLAGS.optimizer == "ftrl":
         # rows seen = rows whose accumulator left its initial value (every worker's shard)
         seen = model.W.slots["Ftrl"] != float(model.W.opt_hp.get("initial_accumulator_value", 0.1))
