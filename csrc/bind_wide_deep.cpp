@@ -7,7 +7,12 @@
 // hipGraph (the capture holds the tensors' and the scratch's addresses).
 #include "bind_common.h"
 #include "eval_record_host.h"
+//
+// The one-GPU fused training step's per-row half is WideDeepTrainPlan
+// (csrc/kernels/wide_deep_train.hip wd_train_rows + wd_train_sums): the same
+// tensors, plus the step's scratch (activations, their gradients, per-row loss).
 #include "kernels/wide_deep_eval.h"
+#include "kernels/wide_deep_train.h"
 
 #include <stdexcept>
 #include <string>
@@ -15,28 +20,29 @@
 
 namespace dtf {
 
-class WideDeepEvalPlan {
+// The model's tensors, checked once: what both plans hold.  `who` prefixes the messages.
+class WideDeepTensors {
  public:
-  WideDeepEvalPlan(at::Tensor wide, at::Tensor emb, std::vector<at::Tensor> layers, at::Tensor bias,
-                   const std::string& combiner)
+  WideDeepTensors(const char* who, at::Tensor wide, at::Tensor emb, std::vector<at::Tensor> layers, at::Tensor bias,
+                  const std::string& combiner)
       : wide_(wide), emb_(emb), layers_(std::move(layers)), bias_(bias) {
     TORCH_CHECK(emb.is_cuda() && emb.scalar_type() == at::kFloat && emb.is_contiguous() && emb.dim() == 2,
-                "WideDeepEvalPlan: emb_table must be a contiguous fp32 [F, D] GPU table");
+                who, ": emb_table must be a contiguous fp32 [F, D] GPU table");
     TORCH_CHECK((reinterpret_cast<uintptr_t>(emb.data_ptr()) & 15) == 0,
-                "WideDeepEvalPlan: unsupported shape (emb_table must be 16-byte aligned)");
+                who, ": unsupported shape (emb_table must be 16-byte aligned)");
     const int64_t F = emb.size(0), D = emb.size(1);
     const int dev = emb.get_device();
     TORCH_CHECK(wide.is_cuda() && wide.scalar_type() == at::kFloat && wide.is_contiguous() && wide.numel() == F &&
                     wide.get_device() == dev && (wide.dim() == 1 || (wide.dim() == 2 && wide.size(1) == 1)),
-                "WideDeepEvalPlan: wide_table must be a contiguous fp32 [F, 1] GPU table on emb_table's device");
+                who, ": wide_table must be a contiguous fp32 [F, 1] GPU table on emb_table's device");
     TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat && bias.numel() == 1 && bias.is_contiguous() &&
                     bias.get_device() == dev,
-                "WideDeepEvalPlan: bias must be one fp32 GPU value");
+                who, ": bias must be one fp32 GPU value");
     TORCH_CHECK(combiner == "sum" || combiner == "mean" || combiner == "sqrtn",
-                "WideDeepEvalPlan: combiner must be sum, mean or sqrtn");
+                who, ": combiner must be sum, mean or sqrtn");
     mode_ = combiner == "sum" ? 0 : (combiner == "mean" ? 1 : 2);
     TORCH_CHECK(F >= 1 && layers_.size() % 2 == 0 && layers_.size() >= 4 && layers_.size() <= 2 * dtfk::wde::MAXL,
-                "WideDeepEvalPlan: unsupported shape (1 to 3 hidden layers and the last one, as [W, b] pairs)");
+                who, ": unsupported shape (1 to 3 hidden layers and the last one, as [W, b] pairs)");
     nl_ = (int)layers_.size() / 2;
     dims_[0] = (int)D;
     int64_t k = D;
@@ -46,16 +52,16 @@ class WideDeepEvalPlan {
       TORCH_CHECK(W.is_cuda() && W.scalar_type() == at::kFloat && W.is_contiguous() && W.dim() == 2 &&
                       W.size(0) == k && W.get_device() == dev && b.is_cuda() && b.scalar_type() == at::kFloat &&
                       b.is_contiguous() && b.numel() == W.size(1) && b.get_device() == dev,
-                  "WideDeepEvalPlan: layers must be contiguous fp32 GPU [K, N] weights and [N] biases in a chain");
+                  who, ": layers must be contiguous fp32 GPU [K, N] weights and [N] biases in a chain");
       k = W.size(1);
-      TORCH_CHECK(k <= dtfk::wde::MAXW, "WideDeepEvalPlan: unsupported shape (hidden width above 512)");
+      TORCH_CHECK(k <= dtfk::wde::MAXW, who, ": unsupported shape (hidden width above 512)");
       dims_[l + 1] = (int)k;
       if (l < nl_ - 1)
         TORCH_CHECK(((reinterpret_cast<uintptr_t>(W.data_ptr()) | reinterpret_cast<uintptr_t>(b.data_ptr())) & 15) == 0,
-                    "WideDeepEvalPlan: unsupported shape (tower tensors must be 16-byte aligned)");
+                    who, ": unsupported shape (tower tensors must be 16-byte aligned)");
     }
     TORCH_CHECK(D <= dtfk::wde::MAXD && dtfk_wd_eval_supported((int)D, nl_, dims_) == 1,
-                "WideDeepEvalPlan: unsupported shape (D a multiple of 4 up to 128; 1 to 3 hidden widths, multiples "
+                who, ": unsupported shape (D a multiple of 4 up to 128; 1 to 3 hidden widths, multiples "
                 "of 16 up to 512; last width 1)");
   }
 
@@ -71,15 +77,9 @@ class WideDeepEvalPlan {
     return dtfk_wd_eval_supported((int)D, (int)hidden.size() + 1, dims) == 1;
   }
 
-  // A CSR batch of device tensors (csr_batch) into `record` (eval_out: reset
-  // starts it over, else the batch is added; pred / logits: [B] f32 or None).
-  // Every refusal raises before anything is launched.
-  void evaluate(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals,
-                at::Tensor record, bool reset, c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
-    const int dev = emb_.get_device();
-    const CsrBatch in = csr_batch("WideDeepEvalPlan.evaluate", dev, labels, offsets, ids, vals);
-    const EvalOut o = eval_out("WideDeepEvalPlan", dev, in.B, record, reset, pred, logits);
-    scratch_.ensure(in.B, emb_.options());
+ protected:
+  // the kernels' view of the tensors and a checked CSR batch (outputs left null)
+  dtfk::wde::Args forward_args(const CsrBatch& in) const {
     dtfk::wde::Args a{};
     a.Wt = wide_.data_ptr<float>();
     a.E = emb_.data_ptr<float>();
@@ -98,6 +98,31 @@ class WideDeepEvalPlan {
     a.nl = nl_;
     a.bias = bias_.data_ptr<float>();
     a.B = (int)in.B;
+    return a;
+  }
+
+  at::Tensor wide_, emb_, bias_;
+  std::vector<at::Tensor> layers_;
+  int dims_[dtfk::wde::MAXL + 1] = {0, 0, 0, 0, 0};
+  int nl_ = 0, mode_ = 0;
+};
+
+class WideDeepEvalPlan : public WideDeepTensors {
+ public:
+  WideDeepEvalPlan(at::Tensor wide, at::Tensor emb, std::vector<at::Tensor> layers, at::Tensor bias,
+                   const std::string& combiner)
+      : WideDeepTensors("WideDeepEvalPlan", wide, emb, std::move(layers), bias, combiner) {}
+
+  // A CSR batch of device tensors (csr_batch) into `record` (eval_out: reset
+  // starts it over, else the batch is added; pred / logits: [B] f32 or None).
+  // Every refusal raises before anything is launched.
+  void evaluate(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals,
+                at::Tensor record, bool reset, c10::optional<at::Tensor> pred, c10::optional<at::Tensor> logits) {
+    const int dev = emb_.get_device();
+    const CsrBatch in = csr_batch("WideDeepEvalPlan.evaluate", dev, labels, offsets, ids, vals);
+    const EvalOut o = eval_out("WideDeepEvalPlan", dev, in.B, record, reset, pred, logits);
+    scratch_.ensure(in.B, emb_.options());
+    dtfk::wde::Args a = forward_args(in);
     a.lrow = scratch_.part(0);
     a.prow = scratch_.part(1);
     a.brow = reinterpret_cast<int*>(scratch_.part(2));
@@ -121,12 +146,120 @@ class WideDeepEvalPlan {
   at::Tensor scratch() const { return scratch_.tensor(); }   // thirds: lrow | prow | bad ids per row (int)
 
  private:
-  at::Tensor wide_, emb_, bias_;
-  std::vector<at::Tensor> layers_;
   EvalScratch scratch_{3};
-  int dims_[dtfk::wde::MAXL + 1] = {0, 0, 0, 0, 0};
-  int nl_ = 0, mode_ = 0, tile_ = 0;
+  int tile_ = 0;
   int64_t eval_runs_ = 0;
+};
+
+// The per-row half of the one-GPU training step.  The plan owns the step's
+// scratch, one tensor of `capacity` rows per part:
+//   act[0 .. nl-1] [cap, dims[l]] | dzl[1 .. nl-1] [cap, dims[l]] | demb [cap, D] | dz | lrow | brow (int) | z [cap]
+// reserve() grows it (never inside a stream capture: a captured graph holds the
+// addresses; an outgrown tensor is kept alive for the graphs that hold it).  The
+// accessors return the last batch's rows of a part.
+class WideDeepTrainPlan : public WideDeepTensors {
+ public:
+  WideDeepTrainPlan(at::Tensor wide, at::Tensor emb, std::vector<at::Tensor> layers, at::Tensor bias,
+                    const std::string& combiner)
+      : WideDeepTensors("WideDeepTrainPlan", wide, emb, std::move(layers), bias, combiner) {
+    TORCH_CHECK(dtfk_wd_train_supported(dims_[0], nl_, dims_) == 1, "WideDeepTrainPlan: unsupported shape");
+    for (int l = 0; l < nl_; ++l) row_floats_ += dims_[l] * (l >= 1 ? 2 : 1);
+    row_floats_ += dims_[0] + 4;
+  }
+
+  void reserve(int64_t B) {
+    if (cur_.defined() && cap_ >= B) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    hip_check(hipStreamIsCapturing(cur_stream(), &cs), "WideDeepTrainPlan.reserve");
+    TORCH_CHECK(cs == hipStreamCaptureStatusNone,
+                "WideDeepTrainPlan: the scratch cannot grow inside a stream capture; reserve(rows) before it");
+    if (cur_.defined()) old_.push_back(cur_);
+    cap_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;    // every part starts 16-byte aligned
+    cur_ = at::empty({cap_ * row_floats_}, emb_.options());
+  }
+
+  // The rows kernel on the current stream: forward, head and the backward through
+  // the tower for one CSR batch of device tensors; gscale: the loss's scale per
+  // row (1 / B for a batch mean).  Every refusal raises before anything is launched.
+  void rows(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, double gscale) {
+    const CsrBatch in = csr_batch("WideDeepTrainPlan.rows", emb_.get_device(), labels, offsets, ids, vals);
+    reserve(in.B);
+    dtfk::wdt::Args a{};
+    a.f = forward_args(in);
+    int64_t off = 0;
+    auto part = [&](int width) {
+      float* p = cur_.data_ptr<float>() + off;
+      off += cap_ * width;
+      return p;
+    };
+    for (int l = 0; l < nl_; ++l) a.act[l] = part(dims_[l]);
+    for (int l = 1; l < nl_; ++l) a.dzl[l] = part(dims_[l]);
+    a.demb = part(dims_[0]);
+    a.dz = part(1);
+    a.f.lrow = part(1);
+    a.f.brow = reinterpret_cast<int*>(part(1));
+    a.f.z_out = part(1);
+    a.gscale = (float)gscale;
+    hip_check(dtfk_wd_train_rows(&a, tile_, cur_stream()), "WideDeepTrainPlan: rows kernel");
+    B_ = in.B;
+    ++runs_;
+  }
+
+  // mean(lrow) of the last batch as a new fp32 scalar, and sum(dz) into db_last /
+  // dbias (one fp32 value each, e.g. views of a flat gradient): one small kernel,
+  // float64 sums in a fixed order.
+  at::Tensor sums(at::Tensor db_last, at::Tensor dbias) {
+    TORCH_CHECK(B_ > 0, "WideDeepTrainPlan.sums: no batch yet");
+    const int dev = emb_.get_device();
+    TORCH_CHECK(on_device(db_last, dev, at::kFloat) && db_last.numel() == 1 && on_device(dbias, dev, at::kFloat) &&
+                    dbias.numel() == 1,
+                "WideDeepTrainPlan.sums: db_last / dbias must be one fp32 value each on the plan's GPU");
+    at::Tensor loss = at::empty({}, emb_.options());
+    hip_check(dtfk_wd_train_sums(view(nl_ * 2 + 1, 1).data_ptr<float>(), view(nl_ * 2, 1).data_ptr<float>(), (int)B_,
+                                 loss.data_ptr<float>(), db_last.data_ptr<float>(), dbias.data_ptr<float>(),
+                                 cur_stream()),
+              "WideDeepTrainPlan: sums kernel");
+    return loss;
+  }
+
+  at::Tensor act(int l) const { return checked(l, 0, "act"), view(l, dims_[l]); }
+  at::Tensor dzl(int l) const { return checked(l, 1, "dzl"), view(nl_ + l - 1, dims_[l]); }
+  at::Tensor demb() const { return view(2 * nl_ - 1, dims_[0]); }
+  at::Tensor dz() const { return view(2 * nl_, 1); }
+  at::Tensor lrow() const { return view(2 * nl_ + 1, 1).reshape({B_}); }
+  at::Tensor brow() const { return view(2 * nl_ + 2, 1).reshape({B_}).view(at::kInt); }
+  at::Tensor z() const { return view(2 * nl_ + 3, 1).reshape({B_}); }
+  at::Tensor scratch() const { return cur_; }
+  int64_t row_floats() const { return row_floats_; }
+  int64_t runs() const { return runs_; }
+  void set_tile(int tile) {
+    TORCH_CHECK(tile == 0 || tile == 16 || tile == 32, "WideDeepTrainPlan.set_tile: 0, 16 or 32");
+    tile_ = tile;
+  }
+  int tile_for(int64_t B) const { return tile_ != 0 ? tile_ : dtfk_wd_train_tile((int)B, nl_, dims_); }
+  int64_t lds_bytes(int tile) const { return dtfk_wd_train_lds_bytes(dims_[0], nl_, dims_, tile); }
+
+ private:
+  void checked(int l, int lo, const char* what) const {
+    TORCH_CHECK(l >= lo && l < nl_, "WideDeepTrainPlan.", what, ": layer out of range");
+  }
+  // part k of the scratch in rows()'s order, the last batch's rows: [B, width]
+  at::Tensor view(int k, int width) const {
+    TORCH_CHECK(cur_.defined() && B_ > 0, "WideDeepTrainPlan: no batch yet");
+    int64_t off = 0;
+    for (int i = 0; i < k; ++i) off += cap_ * part_width(i);
+    return cur_.narrow(0, off, B_ * width).view({B_, width});
+  }
+  int part_width(int i) const {
+    if (i < nl_) return dims_[i];
+    if (i < 2 * nl_ - 1) return dims_[i - nl_ + 1];
+    return i == 2 * nl_ - 1 ? dims_[0] : 1;
+  }
+
+  at::Tensor cur_;
+  std::vector<at::Tensor> old_;
+  int64_t cap_ = 0, B_ = 0, row_floats_ = 0, runs_ = 0;
+  int tile_ = 0;
 };
 
 void init_wide_deep(py::module& m) {
@@ -142,6 +275,27 @@ void init_wide_deep(py::module& m) {
       .def("tile_for", &WideDeepEvalPlan::tile_for, py::arg("rows"))
       .def("lds_bytes", &WideDeepEvalPlan::lds_bytes, py::arg("tile"))
       .def("scratch", &WideDeepEvalPlan::scratch);
+  py::class_<WideDeepTrainPlan>(m, "WideDeepTrainPlan")
+      .def(py::init<at::Tensor, at::Tensor, std::vector<at::Tensor>, at::Tensor, const std::string&>(),
+           py::arg("wide_table"), py::arg("emb_table"), py::arg("layers"), py::arg("bias"), py::arg("combiner") = "sum")
+      .def_static("supported", &WideDeepTrainPlan::supported, py::arg("emb_dim"), py::arg("hidden"))
+      .def("reserve", &WideDeepTrainPlan::reserve, py::arg("rows"))
+      .def("rows", &WideDeepTrainPlan::rows, py::arg("labels"), py::arg("offsets"), py::arg("ids"), py::arg("vals"),
+           py::arg("gscale"))
+      .def("sums", &WideDeepTrainPlan::sums, py::arg("db_last"), py::arg("dbias"))
+      .def("act", &WideDeepTrainPlan::act, py::arg("layer"))
+      .def("dzl", &WideDeepTrainPlan::dzl, py::arg("layer"))
+      .def("demb", &WideDeepTrainPlan::demb)
+      .def("dz", &WideDeepTrainPlan::dz)
+      .def("lrow", &WideDeepTrainPlan::lrow)
+      .def("brow", &WideDeepTrainPlan::brow)
+      .def("z", &WideDeepTrainPlan::z)
+      .def("scratch", &WideDeepTrainPlan::scratch)
+      .def("row_floats", &WideDeepTrainPlan::row_floats)
+      .def("runs", &WideDeepTrainPlan::runs)
+      .def("set_tile", &WideDeepTrainPlan::set_tile, py::arg("tile"))
+      .def("tile_for", &WideDeepTrainPlan::tile_for, py::arg("rows"))
+      .def("lds_bytes", &WideDeepTrainPlan::lds_bytes, py::arg("tile"));
 }
 
 }  // namespace dtf

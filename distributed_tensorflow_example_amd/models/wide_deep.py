@@ -44,7 +44,8 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
                  lr: float = 0.05, dense_lr: Optional[float] = None, dense_opt: str = "sgd", combiner: str = "sum",
                  world: Optional[World] = None, seed: int = 1, device=None, emb_std: float = 0.05,
                  ids_capacity: Optional[int] = None, rows: int = 4096, peer_capacity: Optional[int] = None,
-                 sparse_opt: str = "sgd", sparse_hp: Optional[dict] = None, auc_bins: int = 200):
+                 sparse_opt: str = "sgd", sparse_hp: Optional[dict] = None, auc_bins: int = 200,
+                 fused_step: Optional[bool] = None):
         self.world = world or get_world()
         self.device = torch.device(device) if device is not None else self.world.device
         self.lr = float(lr)
@@ -61,6 +62,15 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
         # the tables' owner-side rule: sgd (TF ScatterSub) | adagrad | momentum | rmsprop | ftrl | adam
         for t in (self.wide, self.emb):
             t.set_optimizer(sparse_opt, **(sparse_hp or {}))
+        self.sparse_opt = sparse_opt
+        # the one-GPU fused training step (_train_step_fused): off unless asked for;
+        # DTF_WD_TRAIN_FUSED=1 turns it on where the argument is left at its default
+        if fused_step is None:
+            import os
+            fused_step = os.environ.get("DTF_WD_TRAIN_FUSED", "0") == "1"
+        self.fused_step = bool(fused_step)
+        self._train_fused = None
+        self._train_plan = None
         self.rows = int(rows)              # batch rows of the captured step
         self._window = []                  # static steps since the router's last check (replay source)
         self._example = None
@@ -188,8 +198,63 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
         offsets[-1] = n
         return (torch.zeros(rows, 1), offsets, torch.zeros(n, dtype=torch.int64), torch.zeros(n))
 
+    def _train_fused_ok(self) -> bool:
+        """fused_step asked for, one worker on a GPU, no Hogwild table, sparse SGD and
+        a tower wd_train_rows takes: every table row is local, and the step is
+        _train_step_fused.  Everything else trains on the general path."""
+        ok = self._train_fused
+        if ok is None:
+            ok = (self.fused_step and self.world.world_size == 1 and self.device.type == "cuda"
+                  and self.wide.hogwild is None and self.emb.hogwild is None
+                  and self.emb.local.shape[0] == self.emb.num_rows and self.sparse_opt == "sgd")
+            if ok:
+                from .. import _native
+                hidden = [int(w.shape[1]) for w in self.layers[0:-2:2]]
+                ok = bool(_native.load().WideDeepTrainPlan.supported(int(self.emb.dim), hidden))
+            self._train_fused = ok
+        return ok
+
+    def _native_train_plan(self):
+        plan = self._train_plan
+        if plan is None:
+            from .. import _native
+            # the plan holds the tensors themselves: it reads what the optimizers last wrote
+            plan = self._train_plan = _native.load().WideDeepTrainPlan(
+                self.wide.local, self.emb.local, [p.data for p in self.layers], self.bias.data, self.combiner)
+        return plan
+
+    @torch.no_grad()
+    def _train_step_fused(self, batch) -> torch.Tensor:
+        """One step without router, dedup or autograd (csrc/kernels/wide_deep_train.hip):
+        wd_train_rows leaves act[l], dzl[l], demb and dz; the dense gradients are
+        written (beta = 0) into the flat_grad views by the general path's gemm /
+        col_sum launches, the tables take the scatter-SGD, the tower its optimizer."""
+        from .. import _native
+        C = _native.load()
+        labels, offsets, ids, vals = batch
+        labels = labels.reshape(-1).float().contiguous()
+        offsets, ids = offsets.long().contiguous(), ids.long().contiguous()
+        vals = None if vals is None else vals.float().contiguous()
+        plan = self._native_train_plan()
+        plan.rows(labels, offsets, ids, vals, 1.0 / labels.numel())
+        nl = len(self.layers) // 2
+        for l in range(nl - 1):
+            dzl = plan.dzl(l + 1)
+            C.gemm(plan.act(l), True, dzl, False, self.layers[2 * l].grad, None, 0, 1.0, 0.0, None)
+            C.col_sum(dzl, self.layers[2 * l + 1].grad)
+        dz = plan.dz()
+        C.gemm(plan.act(nl - 1), True, dz, False, self.layers[-2].grad, None, 0, 1.0, 0.0, None)
+        loss = plan.sums(self.layers[-1].grad, self.bias.grad)      # mean loss; sum(dz) -> both biases' gradients
+        ops.embedding_bag_sgd_(self.emb.local, ids, offsets, vals, plan.demb(), self.lr, self.combiner)
+        ops.embedding_bag_sgd_(self.wide.local, ids, offsets, vals, dz, self.lr)
+        self.opt.step()
+        return loss
+
     def _train_step(self, batch, exact: bool = False) -> torch.Tensor:
         labels, offsets, ids, vals = batch.to(self.device) if hasattr(batch, "to") else batch
+        if self._train_fused_ok():
+            return self._train_step_fused((labels.to(self.device), offsets.to(self.device), ids.to(self.device),
+                                           None if vals is None else vals.to(self.device)))
         self.flat_grad.zero_()
         wide, h, (wrows, erows, lctx) = self.forward_parts(labels, offsets, ids, vals, exact)
         loss = ops.logit3_xent(wide, h, self.bias, labels)      # the head's adds + xent + mean: one kernel
