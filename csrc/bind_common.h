@@ -6,6 +6,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include "kernels/optim_rules.h"
+
 #include <stdexcept>
 #include <string>
 
@@ -51,5 +53,23 @@ inline T* opt_ptr(const c10::optional<at::Tensor>& t) {
   return t.has_value() ? t->data_ptr<T>() : nullptr;
 }
 inline void* opt_ptr(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
+
+// The optimizers' hyper-parameters, under the same keyword names in multi_tensor_apply, sparse_rows_apply
+// and WideDeepTrainPlan.update (optim/rules.py: native_kwargs fills them); each kind reads its own.
+inline dtfk::OptimHyper optim_hyper(double lr, const py::kwargs& kw) {
+  size_t used = 0;
+  auto get = [&](const char* k, double dflt) {
+    if (!kw.contains(k)) return (float)dflt;
+    ++used;
+    return (float)py::cast<double>(kw[k]);
+  };
+  dtfk::OptimHyper h;
+  h.lr = (float)lr; h.momentum = get("momentum", 0.0); h.decay = get("decay", 0.9); h.eps = get("eps", 1e-10);
+  h.nesterov = get("nesterov", 0.0) != 0.f;
+  h.p = -get("lr_power", -0.5); h.l1 = get("l1", 0.0); h.l2 = get("l2", 0.0); h.shrink = get("l2_shrinkage", 0.0);
+  h.beta1 = get("beta1", 0.9); h.beta2 = get("beta2", 0.999); h.weight_decay = get("weight_decay", 0.0);
+  if (used != kw.size()) throw py::type_error("unknown optimizer hyper-parameter among the keyword arguments");
+  return h;
+}
 
 }  // namespace dtf

@@ -365,24 +365,7 @@ void auc_hist(at::Tensor pred, at::Tensor label, at::Tensor pos, at::Tensor neg)
             "auc_hist");
 }
 
-// The optimizers' hyper-parameters, under the same keyword names in multi_tensor_apply and
-// sparse_rows_apply (optim/rules.py: native_kwargs fills them); each kind reads its own.
-static dtfk::OptimHyper optim_hyper(double lr, const py::kwargs& kw) {
-  size_t used = 0;
-  auto get = [&](const char* k, double dflt) {
-    if (!kw.contains(k)) return (float)dflt;
-    ++used;
-    return (float)py::cast<double>(kw[k]);
-  };
-  dtfk::OptimHyper h;
-  h.lr = (float)lr; h.momentum = get("momentum", 0.0); h.decay = get("decay", 0.9); h.eps = get("eps", 1e-10);
-  h.nesterov = get("nesterov", 0.0) != 0.f;
-  h.p = -get("lr_power", -0.5); h.l1 = get("l1", 0.0); h.l2 = get("l2", 0.0); h.shrink = get("l2_shrinkage", 0.0);
-  h.beta1 = get("beta1", 0.9); h.beta2 = get("beta2", 0.999); h.weight_decay = get("weight_decay", 0.0);
-  if (used != kw.size()) throw py::type_error("unknown optimizer hyper-parameter among the keyword arguments");
-  return h;
-}
-
+// optim_hyper (the optimizers' hyper-parameter keywords): bind_common.h
 void multi_tensor_apply(at::Tensor tab, at::Tensor chunks, int kind, bool grad_bf16,
                         c10::optional<at::Tensor> lr_t, double lr, double gscale, c10::optional<at::Tensor> step,
                         c10::optional<at::Tensor> skip, const py::kwargs& hyper) {

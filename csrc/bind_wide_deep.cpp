@@ -13,6 +13,12 @@
 // tensors, plus the step's scratch (activations, their gradients, per-row loss).
 #include "kernels/wide_deep_eval.h"
 #include "kernels/wide_deep_train.h"
+//
+// WideDeepTrainPlan.update is the step's table half (csrc/kernels/wide_deep_update.hip
+// wd_update_runs + wd_update_carry): one stable sort of the batch's ids, then every
+// touched row of both tables written once by a row-local rule of optim_rules.h.
+#include "kernels/ops_api.h"
+#include "kernels/wide_deep_update.h"
 
 #include <stdexcept>
 #include <string>
@@ -167,15 +173,25 @@ class WideDeepTrainPlan : public WideDeepTensors {
     row_floats_ += dims_[0] + 4;
   }
 
-  void reserve(int64_t B) {
-    if (cur_.defined() && cap_ >= B) return;
+  // ids > 0 also sizes update()'s scratch: scale [cap] | bag_of [ids cap] (int) | part (wide_deep_update.h)
+  void reserve(int64_t B, int64_t ids) {
+    const bool rows_ok = cur_.defined() && cap_ >= B, ids_ok = ids <= 0 || (upd_.defined() && ucap_ >= ids && ubag_ >= B);
+    if (rows_ok && ids_ok) return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     hip_check(hipStreamIsCapturing(cur_stream(), &cs), "WideDeepTrainPlan.reserve");
     TORCH_CHECK(cs == hipStreamCaptureStatusNone,
                 "WideDeepTrainPlan: the scratch cannot grow inside a stream capture; reserve(rows) before it");
-    if (cur_.defined()) old_.push_back(cur_);
-    cap_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;    // every part starts 16-byte aligned
-    cur_ = at::empty({cap_ * row_floats_}, emb_.options());
+    if (!rows_ok) {
+      if (cur_.defined()) old_.push_back(cur_);
+      cap_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;    // every part starts 16-byte aligned
+      cur_ = at::empty({cap_ * row_floats_}, emb_.options());
+    }
+    if (!ids_ok) {
+      if (upd_.defined()) old_.push_back(upd_);
+      ucap_ = (std::max<int64_t>(ids, 1024) + 1023) / 1024 * 1024;
+      ubag_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;
+      upd_ = at::empty({ubag_ + ucap_ + dtfk_wd_update_part_floats(ucap_, dims_[0])}, emb_.options());
+    }
   }
 
   // The rows kernel on the current stream: forward, head and the backward through
@@ -183,7 +199,7 @@ class WideDeepTrainPlan : public WideDeepTensors {
   // row (1 / B for a batch mean).  Every refusal raises before anything is launched.
   void rows(at::Tensor labels, at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, double gscale) {
     const CsrBatch in = csr_batch("WideDeepTrainPlan.rows", emb_.get_device(), labels, offsets, ids, vals);
-    reserve(in.B);
+    reserve(in.B, 0);
     dtfk::wdt::Args a{};
     a.f = forward_args(in);
     int64_t off = 0;
@@ -222,6 +238,79 @@ class WideDeepTrainPlan : public WideDeepTensors {
     return loss;
   }
 
+  // The tables' half of the step, after rows(): both tables and their slots take
+  // rule `kind` (optim_rules.h OptimKind, row-local kinds) with the last batch's
+  // demb / dz: duplicates summed, every touched row written once.  offsets / ids /
+  // vals: the batch rows() saw; *_slots: slot a, slot b as the kind has them; skip:
+  // device int32 word (nonzero changes nothing) or None; hyper: Rule.native_kwargs.
+  // One stable sort, bag_index, the combiner's scale and two launches on the current
+  // stream; every refusal raises before anything is launched.
+  void update(at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, int kind, double lr,
+              std::vector<at::Tensor> wide_slots, std::vector<at::Tensor> emb_slots, c10::optional<at::Tensor> skip,
+              const py::kwargs& hyper) {
+    const char* who = "WideDeepTrainPlan.update";
+    const int dev = emb_.get_device();
+    TORCH_CHECK(B_ > 0, who, ": no batch yet (rows() first)");
+    TORCH_CHECK(on_device(offsets, dev, at::kLong) && offsets.numel() == B_ + 1, who,
+                ": offsets must be contiguous int64 on the plan's GPU, B + 1 entries of the last rows() batch");
+    TORCH_CHECK(on_device(ids, dev, at::kLong), who, ": ids must be contiguous int64 on the plan's GPU");
+    const int64_t N = ids.numel(), V = emb_.size(0), D = dims_[0];
+    TORCH_CHECK(!vals.has_value() || (on_device(*vals, dev, at::kFloat) && vals->numel() == N), who,
+                ": vals must be contiguous fp32 on the plan's GPU, one per id");
+    TORCH_CHECK(!skip.has_value() || (on_device(*skip, dev, at::kInt) && skip->numel() >= 1), who,
+                ": skip must be a device int32 word");
+    TORCH_CHECK(wide_slots.size() <= 2 && emb_slots.size() == wide_slots.size(), who,
+                ": up to two slots per table, the same number for both");
+    for (size_t i = 0; i < wide_slots.size(); ++i) {
+      TORCH_CHECK(on_device(wide_slots[i], dev, at::kFloat) && wide_slots[i].numel() == V, who,
+                  ": a wide slot must be contiguous fp32 of the table's shape");
+      TORCH_CHECK(on_device(emb_slots[i], dev, at::kFloat) && emb_slots[i].sizes() == emb_.sizes() &&
+                      (reinterpret_cast<uintptr_t>(emb_slots[i].data_ptr()) & 15) == 0,
+                  who, ": an embedding slot must be contiguous fp32 of the table's shape, 16-byte aligned");
+    }
+    dtfk::wdu::Args a{};
+    a.kind = kind;
+    a.h = optim_hyper(lr, hyper);
+    a.D = (int)D;
+    a.V = V;
+    a.N = N;
+    a.wide = wide_.data_ptr<float>();
+    a.emb = emb_.data_ptr<float>();
+    if (wide_slots.size() >= 1) a.wide_a = wide_slots[0].data_ptr<float>(), a.emb_a = emb_slots[0].data_ptr<float>();
+    if (wide_slots.size() >= 2) a.wide_b = wide_slots[1].data_ptr<float>(), a.emb_b = emb_slots[1].data_ptr<float>();
+    // the launcher's refusals, before the sort is launched
+    TORCH_CHECK(dtfk::row_local(kind) && !(dtfk::uses_slot_a(kind) && a.wide_a == nullptr) &&
+                    !(dtfk::uses_slot_b(kind) && a.wide_b == nullptr) &&
+                    !(kind == dtfk::OPT_FTRL && !dtfk::ftrl_hyper_ok(a.h)) && D % 4 == 0 && D >= 4 &&
+                    D <= dtfk::wdu::MAXD && V < (int64_t(1) << 31) && N < (int64_t(1) << 31),
+                who, ": invalid argument (a row-local kind with its slots, FTRL hyper-parameters >= 0, D a multiple "
+                "of 4 in 4 .. 128, fewer than 2^31 table rows and ids)");
+    if (N == 0) return;
+    reserve(B_, N);
+    hipStream_t st = cur_stream();
+    // ids outside the table become -1 / V: the two ends of the sorted order
+    auto sorted = at::sort(at::clamp(ids, -1, V).to(at::kInt), /*stable=*/true, 0, false);
+    const at::Tensor sids = std::get<0>(sorted).contiguous(), perm = std::get<1>(sorted).contiguous();
+    float* scale = upd_.data_ptr<float>();
+    int* bag_of = reinterpret_cast<int*>(scale + ubag_);
+    hip_check(dtfk_bag_index(offsets.data_ptr<int64_t>(), (int)B_, bag_of, N, st), "WideDeepTrainPlan.update: bag_index");
+    if (mode_ != 0)
+      hip_check(dtfk_wd_update_scale(reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()),
+                                     opt_ptr<float>(vals), (int)B_, mode_, scale, st),
+                "WideDeepTrainPlan.update: scale kernel");
+    a.sids = sids.data_ptr<int>();
+    a.perm = reinterpret_cast<const long long*>(perm.data_ptr<int64_t>());
+    a.bag_of = bag_of;
+    a.vals = opt_ptr<float>(vals);
+    a.scale = mode_ != 0 ? scale : nullptr;
+    a.dz = view(2 * nl_, 1).data_ptr<float>();
+    a.demb = view(2 * nl_ - 1, dims_[0]).data_ptr<float>();
+    a.part = scale + ubag_ + ucap_;
+    a.skip = opt_ptr<int>(skip);
+    hip_check(dtfk_wd_update(&a, st), "WideDeepTrainPlan.update");
+    ++updates_;
+  }
+
   at::Tensor act(int l) const { return checked(l, 0, "act"), view(l, dims_[l]); }
   at::Tensor dzl(int l) const { return checked(l, 1, "dzl"), view(nl_ + l - 1, dims_[l]); }
   at::Tensor demb() const { return view(2 * nl_ - 1, dims_[0]); }
@@ -232,6 +321,7 @@ class WideDeepTrainPlan : public WideDeepTensors {
   at::Tensor scratch() const { return cur_; }
   int64_t row_floats() const { return row_floats_; }
   int64_t runs() const { return runs_; }
+  int64_t updates() const { return updates_; }
   void set_tile(int tile) {
     TORCH_CHECK(tile == 0 || tile == 16 || tile == 32, "WideDeepTrainPlan.set_tile: 0, 16 or 32");
     tile_ = tile;
@@ -256,9 +346,10 @@ class WideDeepTrainPlan : public WideDeepTensors {
     return i == 2 * nl_ - 1 ? dims_[0] : 1;
   }
 
-  at::Tensor cur_;
+  at::Tensor cur_, upd_;
   std::vector<at::Tensor> old_;
   int64_t cap_ = 0, B_ = 0, row_floats_ = 0, runs_ = 0;
+  int64_t ucap_ = 0, ubag_ = 0, updates_ = 0;
   int tile_ = 0;
 };
 
@@ -279,10 +370,13 @@ void init_wide_deep(py::module& m) {
       .def(py::init<at::Tensor, at::Tensor, std::vector<at::Tensor>, at::Tensor, const std::string&>(),
            py::arg("wide_table"), py::arg("emb_table"), py::arg("layers"), py::arg("bias"), py::arg("combiner") = "sum")
       .def_static("supported", &WideDeepTrainPlan::supported, py::arg("emb_dim"), py::arg("hidden"))
-      .def("reserve", &WideDeepTrainPlan::reserve, py::arg("rows"))
+      .def("reserve", &WideDeepTrainPlan::reserve, py::arg("rows"), py::arg("ids") = 0)
       .def("rows", &WideDeepTrainPlan::rows, py::arg("labels"), py::arg("offsets"), py::arg("ids"), py::arg("vals"),
            py::arg("gscale"))
       .def("sums", &WideDeepTrainPlan::sums, py::arg("db_last"), py::arg("dbias"))
+      .def("update", &WideDeepTrainPlan::update, py::arg("offsets"), py::arg("ids"), py::arg("vals"), py::arg("kind"),
+           py::arg("lr"), py::arg("wide_slots"), py::arg("emb_slots"), py::arg("skip") = py::none())
+      .def("updates", &WideDeepTrainPlan::updates)
       .def("act", &WideDeepTrainPlan::act, py::arg("layer"))
       .def("dzl", &WideDeepTrainPlan::dzl, py::arg("layer"))
       .def("demb", &WideDeepTrainPlan::demb)

@@ -114,4 +114,24 @@ __device__ __forceinline__ void ftrl_update(float& var, float& acc, float& lin, 
 }
 #endif  // __HIPCC__
 
+// The kinds that update only the rows a gradient touches: what the row kernels
+// take (sparse_optim.hip: rows_apply, wide_deep_update.hip).  Adam is not one.
+constexpr __host__ __device__ bool row_local(int kind) {
+  return kind == OPT_SGD || kind == OPT_MOMENTUM || kind == OPT_ADAGRAD || kind == OPT_RMSPROP || kind == OPT_FTRL;
+}
+
+#ifdef __HIPCC__
+// One element of a row-local kind, the row kernels' form (FAST_RSQRT); a, b: its
+// slots.  `kind` is a run-time, wave-uniform branch.
+__device__ __forceinline__ void update1(float& var, float& a, float& b, float g, int kind, const OptimHyper& h) {
+  switch (kind) {
+    case OPT_SGD: rule_sgd(var, g, h.lr); break;
+    case OPT_MOMENTUM: rule_momentum(var, a, g, h.lr, h); break;
+    case OPT_ADAGRAD: rule_adagrad<true>(var, a, g, h.lr); break;
+    case OPT_RMSPROP: rule_rmsprop<true>(var, a, b, g, h.lr, h); break;
+    default: ftrl_update(var, a, b, g, h.lr, h.p, h.l1, h.l2, h.shrink); break;   // OPT_FTRL
+  }
+}
+#endif  // __HIPCC__
+
 }  // namespace dtfk

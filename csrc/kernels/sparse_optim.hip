@@ -25,20 +25,7 @@
 namespace dtfk {
 namespace sparse_optim {
 
-constexpr bool row_local(int kind) {
-  return kind == OPT_SGD || kind == OPT_MOMENTUM || kind == OPT_ADAGRAD || kind == OPT_RMSPROP || kind == OPT_FTRL;
-}
-
-// `kind` is a run-time, wave-uniform branch
-__device__ __forceinline__ void update1(float& var, float& a, float& b, float g, int kind, const OptimHyper& h) {
-  switch (kind) {
-    case OPT_SGD: rule_sgd(var, g, h.lr); break;
-    case OPT_MOMENTUM: rule_momentum(var, a, g, h.lr, h); break;
-    case OPT_ADAGRAD: rule_adagrad<true>(var, a, g, h.lr); break;
-    case OPT_RMSPROP: rule_rmsprop<true>(var, a, b, g, h.lr, h); break;
-    default: ftrl_update(var, a, b, g, h.lr, h.p, h.l1, h.l2, h.shrink); break;   // OPT_FTRL
-  }
-}
+// row_local(kind) and update1 (one element of a row-local kind): optim_rules.h
 
 template <int V>
 __global__ __launch_bounds__(256) void rows_apply(float* __restrict__ table, float* __restrict__ slot_a,

@@ -64,10 +64,16 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
             t.set_optimizer(sparse_opt, **(sparse_hp or {}))
         self.sparse_opt = sparse_opt
         # the one-GPU fused training step (_train_step_fused): off unless asked for;
-        # DTF_WD_TRAIN_FUSED=1 turns it on where the argument is left at its default
+        # DTF_WD_TRAIN_FUSED=1 turns it on where the argument is left at its default.
+        # "combined" (DTF_WD_TRAIN_FUSED=combined): the fused step with the one-writer
+        # table update (csrc/kernels/wide_deep_update.hip), for every row-local sparse_opt
         if fused_step is None:
             import os
-            fused_step = os.environ.get("DTF_WD_TRAIN_FUSED", "0") == "1"
+            env = os.environ.get("DTF_WD_TRAIN_FUSED", "0")
+            fused_step = "combined" if env == "combined" else env == "1"
+        if isinstance(fused_step, str) and fused_step != "combined":
+            raise ValueError(f"fused_step: True, False or 'combined', not '{fused_step}'")
+        self.fused_combined = fused_step == "combined"
         self.fused_step = bool(fused_step)
         self._train_fused = None
         self._train_plan = None
@@ -199,14 +205,16 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
         return (torch.zeros(rows, 1), offsets, torch.zeros(n, dtype=torch.int64), torch.zeros(n))
 
     def _train_fused_ok(self) -> bool:
-        """fused_step asked for, one worker on a GPU, no Hogwild table, sparse SGD and
-        a tower wd_train_rows takes: every table row is local, and the step is
-        _train_step_fused.  Everything else trains on the general path."""
+        """fused_step asked for, one worker on a GPU, no Hogwild table, sparse SGD
+        (fused_step="combined": any row-local sparse_opt) and a tower wd_train_rows
+        takes: every table row is local, and the step is _train_step_fused.
+        Everything else trains on the general path."""
         ok = self._train_fused
         if ok is None:
+            rule_ok = optim.RULES[self.sparse_opt].row_local if self.fused_combined else self.sparse_opt == "sgd"
             ok = (self.fused_step and self.world.world_size == 1 and self.device.type == "cuda"
                   and self.wide.hogwild is None and self.emb.hogwild is None
-                  and self.emb.local.shape[0] == self.emb.num_rows and self.sparse_opt == "sgd")
+                  and self.emb.local.shape[0] == self.emb.num_rows and rule_ok)
             if ok:
                 from .. import _native
                 hidden = [int(w.shape[1]) for w in self.layers[0:-2:2]]
@@ -228,7 +236,8 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
         """One step without router, dedup or autograd (csrc/kernels/wide_deep_train.hip):
         wd_train_rows leaves act[l], dzl[l], demb and dz; the dense gradients are
         written (beta = 0) into the flat_grad views by the general path's gemm /
-        col_sum launches, the tables take the scatter-SGD, the tower its optimizer."""
+        col_sum launches, the tables take the scatter-SGD (fused_step="combined": their
+        sparse_opt rule from one sorted pass, plan.update), the tower its optimizer."""
         from .. import _native
         C = _native.load()
         labels, offsets, ids, vals = batch
@@ -245,8 +254,15 @@ class WideDeep(StreamingEvalMixin, StaticStepMixin):
         dz = plan.dz()
         C.gemm(plan.act(nl - 1), True, dz, False, self.layers[-2].grad, None, 0, 1.0, 0.0, None)
         loss = plan.sums(self.layers[-1].grad, self.bias.grad)      # mean loss; sum(dz) -> both biases' gradients
-        ops.embedding_bag_sgd_(self.emb.local, ids, offsets, vals, plan.demb(), self.lr, self.combiner)
-        ops.embedding_bag_sgd_(self.wide.local, ids, offsets, vals, dz, self.lr)
+        if self.fused_combined:
+            # both tables by their rule, every touched row written once (wide_deep_update.hip);
+            # an empty batch (all padding) touches no row: the tables' device word
+            rule = optim.RULES[self.sparse_opt]
+            plan.update(offsets, ids, vals, rule.kind, self.lr, list(self.wide.slots.values()),
+                        list(self.emb.slots.values()), self.wide._empty, **rule.native_kwargs(self.wide.opt_hp))
+        else:
+            ops.embedding_bag_sgd_(self.emb.local, ids, offsets, vals, plan.demb(), self.lr, self.combiner)
+            ops.embedding_bag_sgd_(self.wide.local, ids, offsets, vals, dz, self.lr)
         self.opt.step()
         return loss
 

@@ -87,8 +87,10 @@ def main():
     ap.add_argument("--sparse-opt", default="sgd", choices=["sgd", "adagrad", "momentum", "rmsprop", "adam", "ftrl"],
                     help="wide_deep: the tables' owner-side update rule; sparse_lr / lr2: sgd or ftrl")
     ap.add_argument("--graph", action="store_true", help="sparse_lr / lr2 / wide_deep: replay each step as one captured hipGraph")
-    ap.add_argument("--fused-step", action="store_true",
-                    help="wide_deep on one GPU: the fused training step (csrc/kernels/wide_deep_train.hip)")
+    ap.add_argument("--fused-step", nargs="?", const=True, default=False, choices=["combined"],
+                    help="wide_deep on one GPU: the fused training step (csrc/kernels/wide_deep_train.hip); "
+                         "'combined': with the one-writer table update of every row-local --sparse-opt "
+                         "(csrc/kernels/wide_deep_update.hip)")
     ap.add_argument("--trace-marker", action="store_true",
                     help="launch a spin kernel right before the timed loop, so a kernel trace can be cut to the "
                          "steady state (scripts/rocpd_summary.py --after spin)")
@@ -117,13 +119,13 @@ def main():
                      dense_lr=1e-3, world=w, ids_capacity=a.batch * a.nnz if (a.graph or w.world_size > 1) else None,
                      rows=a.batch, sparse_opt=a.sparse_opt, fused_step=a.fused_step)
         if a.fused_step and not m._train_fused_ok():
-            ap.error("--fused-step: one GPU, --sparse-opt sgd and a supported tower")
+            ap.error("--fused-step: one GPU, --sparse-opt sgd (combined: any but adam) and a supported tower")
         if a.graph:
             m.enable_graph()
         cfg = {"model": f"wide_deep F={a.features} D={a.emb_dim} tower=512-256-1", "global_batch": a.batch * w.world_size,
                "per_gpu_batch": a.batch, "seq_len": None, "parallelism": f"dp{w.world_size}+emb-shard{w.world_size}",
                "nnz_per_sample": a.nnz, "graph": bool(a.graph), "sparse_opt": a.sparse_opt,
-               "fused_step": bool(m._train_fused_ok())}
+               "fused_step": ("combined" if m.fused_combined else True) if m._train_fused_ok() else False}
     else:
         from distributed_tensorflow_example_amd.models.sparse_lr import SparseLRTrainer
 
