@@ -23,6 +23,8 @@ void gemm(at::Tensor A, bool transA, at::Tensor B, bool transB, at::Tensor out,
   const int N = (int)(transB ? B.size(0) : B.size(1));
   if (K != KB) throw std::runtime_error("gemm inner dimensions differ");
   if (out.size(0) != M || out.size(1) != N) throw std::runtime_error("gemm out has wrong shape");
+  // the tile loaders clamp k to K - 1: an empty contraction would index in front of the operands
+  if (K == 0) throw std::runtime_error("gemm: K == 0 (an empty inner dimension) is not supported");
   if (bias.has_value()) {
     need(*bias, at::kFloat, "bias");
     require(bias->numel() == N, "bias size");
@@ -30,6 +32,11 @@ void gemm(at::Tensor A, bool transA, at::Tensor B, bool transB, at::Tensor out,
   if (Z.has_value()) {
     need(*Z, at::kFloat, "Z");
     require(Z->size(0) == M && Z->size(1) == N, "Z shape");
+    // the kernels store Z[m * ldc + n] with out's leading dimension ldc; Z itself is contiguous [M, N], so the two
+    // must agree.  A single-row out is exempt: its only offsets are 0 * ldc + n, whatever stride(0) a view reports
+    if (out.stride(0) != N && M > 1)
+      throw std::runtime_error("gemm: Z is written with the row stride of out, so with Z given out must be "
+                               "contiguous (out.stride(0) == N, unless it has one row) like Z");
   }
   hip_check(dtfk_gemm(A.data_ptr(), A.scalar_type() == at::kBFloat16, (int)A.stride(0), transA, B.data_ptr(),
                       B.scalar_type() == at::kBFloat16, (int)B.stride(0), transB, out.data_ptr(),

@@ -155,12 +155,12 @@ def case(name, M, N, K, tA=False, tB=True, variant=8, obf=False, alpha=1.0, beta
                 pc, coff, rng, zlib.crc32(full.encode()), gauss, accumulate, float(scale))
 
 
-def embed(t, p, off=8, fill=float("nan")):
+def embed(t, p, off=8, fill=float("nan"), ld=None):
     """A copy of the 2-D tensor t as a view inside a wider flat parent: the view
-    starts `off` elements in, its row stride is cols + 8 p, and everything
-    outside it is `fill`.  view._base is the parent."""
+    starts `off` elements in, its row stride is cols + 8 p (or `ld` when given),
+    and everything outside it is `fill`.  view._base is the parent."""
     rows, cols = t.shape
-    ld = cols + 8 * p
+    ld = cols + 8 * p if ld is None else ld
     parent = torch.full((off + rows * ld + 8,), fill, dtype=t.dtype)
     view = parent.as_strided((rows, cols), (ld, 1), off)
     view.copy_(t)
