@@ -1,0 +1,1 @@
+from .fm import FMTrainer  # noqa: F401

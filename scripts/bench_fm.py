@@ -1,0 +1,138 @@
+"""Cost of a factorization-machine training step and evaluation on one GPU, through FMTrainer's public interface:
+
+    python scripts/bench_fm.py [--features 100000000] [--rounds 3] [--out FILE]
+
+F = 1e8 features, K = 64 factors, about 40 ids per row (Zipf-hot), SGD, device-resident batches of 500 and 4096
+rows.  Two variants, measured in alternating fresh child processes, `--rounds` each: the fused path
+(csrc/kernels/fm.hip) and the same build with DTF_FM_FUSED=0 (the torch path: gathers, index_add_, unique and
+indexed writes).  The torch path is the baseline: before the kernels there was no factorization machine to time.
+
+Per variant and batch size, the time between two events on the stream around 10 host-issued calls, per call, of
+`train_step` eager, of `train_step` replayed as a captured graph (fused only) and of `evaluate`.  That is wall time on
+the stream: gaps in which the device waits for the host's next launch are inside it, so an eager figure is an upper
+bound on the kernels' time; no kernel trace is taken here.  The fused worker also times `evaluate` at each forced
+rows-per-wave of fm_rows (FMPlan.set_rpw) next to the automatic pick.  Medians over the rounds with min / max; one
+JSON document.
+
+What a step must move at B = 4096: 4096 x 40 table rows x 256 B = 42 MB of random 256-byte reads in fm_rows, and
+per distinct id one 256-byte read and write in the update.
+"""
+import argparse
+import json
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+
+RPWS = (1, 2, 4, 8)
+
+
+def _batch(rng, B, F, per=40):
+    k = rng.integers(per // 2, per * 3 // 2 + 1, B)
+    off = np.zeros(B + 1, np.int64)
+    np.cumsum(k, out=off[1:])
+    n = int(off[-1])
+    ids = np.minimum(rng.zipf(1.2, n) - 1, F - 1).astype(np.int64)
+    return ((rng.random(B) < 0.3).astype(np.float32), off, ids, rng.uniform(0.5, 1.5, n).astype(np.float32))
+
+
+def _stream_ms(torch, fn, reps=20, warmup=5, inner=10):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / inner)
+    return float(np.median(out))
+
+
+def worker(tree, F):
+    sys.path.insert(0, tree)
+    import torch
+
+    from distributed_tensorflow_example_amd.models import FMTrainer
+    from distributed_tensorflow_example_amd.parallel.world import World
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(0)
+    m = FMTrainer(F, factors=64, lr=0.05, world=World(device=dev))
+    res = {"fused": bool(m._fused_ok())}
+    batches = {B: tuple(torch.from_numpy(a).to(dev) for a in _batch(rng, B, F)) for B in (500, 4096)}
+    for B, b in batches.items():
+        res[f"train_step_eager_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.train_step(b))
+        res[f"evaluate_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.evaluate(b))
+    if res["fused"]:
+        plan = m._native_plan()
+        for B, b in batches.items():
+            res[f"rpw_auto_{B}"] = int(plan.rpw_for(B))
+            for r in RPWS:
+                plan.set_rpw(r)
+                res[f"evaluate_{B}_rpw{r}_event_ms"] = _stream_ms(torch, lambda b=b: m.evaluate(b))
+            plan.set_rpw(0)
+        m.enable_graph()
+        for B, b in batches.items():
+            res[f"train_step_graph_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.train_step(b))
+    props = torch.cuda.get_device_properties(0)
+    res["box"] = f"{socket.gethostname()}: {props.name}, {props.gcnArchName}, {props.multi_processor_count} CUs"
+    print("RESULT " + json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--features", type=int, default=100_000_000)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--worker", default="")
+    a = ap.parse_args()
+    if a.worker:
+        return worker(a.worker, a.features)
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    variants = [("fused", {"DTF_FM_FUSED": "1"}), ("general_path", {"DTF_FM_FUSED": "0"})]
+    runs = {name: [] for name, _ in variants}
+    for r in range(a.rounds):
+        # alternating: one process per variant per round, the order reversed every other round
+        for name, env in (variants if r % 2 == 0 else variants[::-1]):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", here, "--features",
+                                str(a.features)], capture_output=True, text=True, env=dict(os.environ, **env),
+                               timeout=300)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                raise SystemExit(f"{name} round {r} failed:\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
+            runs[name].append(json.loads(line[-1][7:]))
+            print(name, r, line[-1][7:], flush=True)
+    out = {"features": a.features, "factors": 64, "optimizer": "sgd", "rounds": a.rounds, "ids_per_row": 40,
+           "table_row_bytes_read_by_fm_rows_at_4096": 4096 * 40 * 256, "variants": {}}
+    for name, rs in runs.items():
+        v = {}
+        for k in rs[0]:
+            xs = [x[k] for x in rs]
+            if k.endswith("_ms"):
+                v[k] = {"median": round(float(np.median(xs)), 5), "min": round(min(xs), 5), "max": round(max(xs), 5)}
+            else:
+                v[k] = xs[-1]
+        out["variants"][name] = v
+    f, g = out["variants"]["fused"], out["variants"]["general_path"]
+    out["box"] = f["box"]
+    out["general_over_fused"] = {k: round(g[k]["median"] / f[k]["median"], 2) for k in g if k.endswith("_ms")}
+    # faster by more than the spread: the fused path's slowest run under the general path's fastest
+    out["fused_faster_beyond_spread"] = {k: bool(f[k]["max"] < g[k]["min"]) for k in g if k.endswith("_ms")}
+    out["rpw"] = {str(B): {"auto": f[f"rpw_auto_{B}"],
+                           **{f"rpw{r}_evaluate_ms": f[f"evaluate_{B}_rpw{r}_event_ms"] for r in RPWS}} for B in (500, 4096)}
+    text = json.dumps(out, indent=1)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
