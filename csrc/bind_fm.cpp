@@ -15,8 +15,8 @@
 // training step's rows between rows() and update().
 #include "bind_common.h"
 #include "eval_record_host.h"
+#include "fm_update_host.h"
 #include "kernels/fm.h"
-#include "kernels/ops_api.h"
 #include "kernels/wide_deep_train.h"
 
 #include <algorithm>
@@ -92,58 +92,14 @@ class FMPlan {
   // Rule.native_kwargs.
   void update(at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, int kind, double lr,
               std::vector<at::Tensor> w_slots, std::vector<at::Tensor> V_slots, const py::kwargs& hyper) {
-    const char* who = "FMPlan.update";
-    const int dev = V_.get_device();
-    TORCH_CHECK(B_ > 0, who, ": no batch yet (rows() first)");
-    TORCH_CHECK(on_device(offsets, dev, at::kLong) && offsets.numel() == B_ + 1, who,
-                ": offsets must be contiguous int64 on the plan's GPU, B + 1 entries of the last rows() batch");
-    TORCH_CHECK(on_device(ids, dev, at::kLong), who, ": ids must be contiguous int64 on the plan's GPU");
-    const int64_t N = ids.numel();
-    TORCH_CHECK(!vals.has_value() || (on_device(*vals, dev, at::kFloat) && vals->numel() == N), who,
-                ": vals must be contiguous fp32 on the plan's GPU, one per id");
-    TORCH_CHECK(w_slots.size() <= 2 && V_slots.size() == w_slots.size(), who,
-                ": up to two slots per table, the same number for both");
-    for (size_t i = 0; i < w_slots.size(); ++i) {
-      TORCH_CHECK(on_device(w_slots[i], dev, at::kFloat) && w_slots[i].numel() == F_, who,
-                  ": a slot of w must be contiguous fp32 of the table's shape");
-      TORCH_CHECK(on_device(V_slots[i], dev, at::kFloat) && V_slots[i].sizes() == V_.sizes() &&
-                      (reinterpret_cast<uintptr_t>(V_slots[i].data_ptr()) & 15) == 0,
-                  who, ": a slot of V must be contiguous fp32 of the table's shape, 16-byte aligned");
-    }
-    dtfk::fm::UpdArgs a{};
-    a.kind = kind;
-    a.h = optim_hyper(lr, hyper);
-    a.K = (int)K_;
-    a.F = F_;
-    a.N = N;
-    a.w = w_.data_ptr<float>();
-    a.V = V_.data_ptr<float>();
-    if (w_slots.size() >= 1) a.w_a = w_slots[0].data_ptr<float>(), a.V_a = V_slots[0].data_ptr<float>();
-    if (w_slots.size() >= 2) a.w_b = w_slots[1].data_ptr<float>(), a.V_b = V_slots[1].data_ptr<float>();
-    // the launcher's refusals, before the sort is launched
-    TORCH_CHECK(dtfk::row_local(kind) && !(dtfk::uses_slot_a(kind) && a.w_a == nullptr) &&
-                    !(dtfk::uses_slot_b(kind) && a.w_b == nullptr) &&
-                    !(kind == dtfk::OPT_FTRL && !dtfk::ftrl_hyper_ok(a.h)) && F_ < (int64_t(1) << 31) &&
-                    N < (int64_t(1) << 31),
-                who, ": invalid argument (a row-local kind with its slots, FTRL hyper-parameters >= 0, fewer than "
-                "2^31 table rows and ids)");
-    if (N == 0) return;
-    reserve(B_, N);
-    hipStream_t st = cur_stream();
-    // ids outside the table become -1 / F: the two ends of the sorted order
-    auto sorted = at::sort(at::clamp(ids, -1, F_).to(at::kInt), /*stable=*/true, 0, false);
-    const at::Tensor sids = std::get<0>(sorted).contiguous(), perm = std::get<1>(sorted).contiguous();
-    int* bag_of = reinterpret_cast<int*>(upd_.data_ptr<float>());
-    hip_check(dtfk_bag_index(offsets.data_ptr<int64_t>(), (int)B_, bag_of, N, st), "FMPlan.update: bag_index");
-    a.sids = sids.data_ptr<int>();
-    a.perm = reinterpret_cast<const long long*>(perm.data_ptr<int64_t>());
-    a.bag_of = bag_of;
-    a.vals = opt_ptr<float>(vals);
-    a.dz = part(1);
-    a.demb = part(0);
-    a.part = upd_.data_ptr<float>() + ucap_;
-    hip_check(dtfk_fm_update(&a, st), "FMPlan.update");
-    ++updates_;
+    TORCH_CHECK(B_ > 0, "FMPlan.update: no batch yet (rows() first)");
+    if (fm_update_host("FMPlan.update", w_, V_, B_, offsets, ids, vals, kind, lr, w_slots, V_slots, hyper, part(1),
+                       part(0), [&](int64_t N) {
+                         reserve(B_, N);
+                         return std::make_pair(reinterpret_cast<int*>(upd_.data_ptr<float>()),
+                                               upd_.data_ptr<float>() + ucap_);
+                       }))
+      ++updates_;
   }
 
   // fm_rows<false> and the record's reduce: the batch into `record` (reset starts it

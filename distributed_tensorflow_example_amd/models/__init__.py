@@ -1,1 +1,2 @@
+from .deepfm import DeepFMTrainer  # noqa: F401
 from .fm import FMTrainer  # noqa: F401

@@ -1,6 +1,6 @@
 """Cost of a factorization-machine training step and evaluation on one GPU, through FMTrainer's public interface:
 
-    python scripts/bench_fm.py [--features 100000000] [--rounds 3] [--out FILE]
+    python scripts/bench_fm.py [--features 100000000] [--rounds 3] [--out FILE] [--hidden 512,256]
 
 F = 1e8 features, K = 64 factors, about 40 ids per row (Zipf-hot), SGD, device-resident batches of 500 and 4096
 rows.  Two variants, measured in alternating fresh child processes, `--rounds` each: the fused path
@@ -13,6 +13,10 @@ the stream: gaps in which the device waits for the host's next launch are inside
 bound on the kernels' time; no kernel trace is taken here.  The fused worker also times `evaluate` at each forced
 rows-per-wave of fm_rows (FMPlan.set_rpw) next to the automatic pick.  Medians over the rounds with min / max; one
 JSON document.
+
+--hidden W1,W2,..: the same for DeepFM (models/deepfm.py DeepFMTrainer with that tower, csrc/kernels/deepfm.hip):
+its fused path against its torch path (DTF_DFM_FUSED=0, the baseline: there was no DeepFM before), and the plain
+fused FM step next to both; no rows-per-wave sweep.  The record then also lists every run of every variant.
 
 What a step must move at B = 4096: 4096 x 40 table rows x 256 B = 42 MB of random 256-byte reads in fm_rows, and
 per distinct id one 256-byte read and write in the update.
@@ -54,17 +58,20 @@ def _stream_ms(torch, fn, reps=20, warmup=5, inner=10):
     return float(np.median(out))
 
 
-def worker(tree, F):
+def worker(tree, F, hidden=()):
     sys.path.insert(0, tree)
     import torch
 
-    from distributed_tensorflow_example_amd.models import FMTrainer
+    from distributed_tensorflow_example_amd.models import DeepFMTrainer, FMTrainer
     from distributed_tensorflow_example_amd.parallel.world import World
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     rng = np.random.default_rng(0)
-    m = FMTrainer(F, factors=64, lr=0.05, world=World(device=dev))
+    if hidden:
+        m = DeepFMTrainer(F, factors=64, hidden=hidden, lr=0.05, world=World(device=dev))
+    else:
+        m = FMTrainer(F, factors=64, lr=0.05, world=World(device=dev))
     res = {"fused": bool(m._fused_ok())}
     batches = {B: tuple(torch.from_numpy(a).to(dev) for a in _batch(rng, B, F)) for B in (500, 4096)}
     for B, b in batches.items():
@@ -72,7 +79,7 @@ def worker(tree, F):
         res[f"evaluate_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.evaluate(b))
     if res["fused"]:
         plan = m._native_plan()
-        for B, b in batches.items():
+        for B, b in ({} if hidden else batches).items():
             res[f"rpw_auto_{B}"] = int(plan.rpw_for(B))
             for r in RPWS:
                 plan.set_rpw(r)
@@ -92,17 +99,21 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default="")
     ap.add_argument("--worker", default="")
+    ap.add_argument("--hidden", default="", help="DeepFM's hidden widths, e.g. 512,256 (default: the plain FM)")
     a = ap.parse_args()
     if a.worker:
-        return worker(a.worker, a.features)
+        return worker(a.worker, a.features, tuple(int(h) for h in a.hidden.split(",") if h))
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    variants = [("fused", {"DTF_FM_FUSED": "1"}), ("general_path", {"DTF_FM_FUSED": "0"})]
-    runs = {name: [] for name, _ in variants}
+    variants = [("fused", {"DTF_FM_FUSED": "1"}, ""), ("general_path", {"DTF_FM_FUSED": "0"}, "")]
+    if a.hidden:
+        variants = [("fused", {"DTF_DFM_FUSED": "1"}, a.hidden), ("general_path", {"DTF_DFM_FUSED": "0"}, a.hidden),
+                    ("fm_fused", {"DTF_FM_FUSED": "1"}, "")]
+    runs = {name: [] for name, _, _ in variants}
     for r in range(a.rounds):
         # alternating: one process per variant per round, the order reversed every other round
-        for name, env in (variants if r % 2 == 0 else variants[::-1]):
+        for name, env, hidden in (variants if r % 2 == 0 else variants[::-1]):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", here, "--features",
-                                str(a.features)], capture_output=True, text=True, env=dict(os.environ, **env),
+                                str(a.features), "--hidden", hidden], capture_output=True, text=True, env=dict(os.environ, **env),
                                timeout=300)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
             if p.returncode != 0 or not line:
@@ -125,8 +136,14 @@ def main():
     out["general_over_fused"] = {k: round(g[k]["median"] / f[k]["median"], 2) for k in g if k.endswith("_ms")}
     # faster by more than the spread: the fused path's slowest run under the general path's fastest
     out["fused_faster_beyond_spread"] = {k: bool(f[k]["max"] < g[k]["min"]) for k in g if k.endswith("_ms")}
-    out["rpw"] = {str(B): {"auto": f[f"rpw_auto_{B}"],
-                           **{f"rpw{r}_evaluate_ms": f[f"evaluate_{B}_rpw{r}_event_ms"] for r in RPWS}} for B in (500, 4096)}
+    if a.hidden:
+        out["hidden"] = [int(h) for h in a.hidden.split(",")]
+        fm = out["variants"]["fm_fused"]
+        out["fused_over_fm_fused"] = {k: round(f[k]["median"] / fm[k]["median"], 2) for k in f if k.endswith("_ms") and k in fm}
+        out["runs"] = {name: {k: [x[k] for x in rs] for k in rs[0] if k.endswith("_ms")} for name, rs in runs.items()}
+    else:
+        out["rpw"] = {str(B): {"auto": f[f"rpw_auto_{B}"],
+                               **{f"rpw{r}_evaluate_ms": f[f"evaluate_{B}_rpw{r}_event_ms"] for r in RPWS}} for B in (500, 4096)}
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
