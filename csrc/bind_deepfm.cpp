@@ -8,16 +8,18 @@
 // eval_record.hip's reduce.  Every refusal raises before anything is launched; no
 // host read-back and no memset node, so a step can be captured in a hipGraph.
 //
-// Scratch, one tensor of `capacity` rows per part, grown only when a batch exceeds
-// it and never inside a stream capture (an outgrown tensor is kept alive for the
-// graphs that hold it):
+// Scratch (step_scratch.h), one tensor of `capacity` rows per part, grown only when
+// a batch exceeds it and never inside a stream capture (an outgrown tensor is kept
+// alive for the graphs that hold it):
 //   rows:   act[0 .. nl-1] [cap, dims[l]] | dzl[1 .. nl-1] [cap, dims[l]] | demb [cap, K] | dz | lrow | brow (int) | z [cap]
-//   update: bag_of [ids cap] (int) | part (fm.h)
+//   update: bag_of [ids cap] (int) | part (table_update.h)
 // An evaluation has per-row arrays of its own (EvalScratch: lrow | prow | brow).
 #include "bind_common.h"
 #include "eval_record_host.h"
-#include "fm_update_host.h"
 #include "kernels/deepfm.h"
+#include "kernels/fm.h"
+#include "step_scratch.h"
+#include "table_update_host.h"
 
 #include <algorithm>
 #include <vector>
@@ -59,8 +61,10 @@ class DeepFMPlan {
     TORCH_CHECK(dtfk_dfm_supported(dims_[0], nl_, dims_) == 1, who,
                 ": unsupported shape (K a multiple of 4 in 4 .. 128; 1 to 3 hidden widths, multiples of 16 up to 512; "
                 "last width 1)");
-    for (int l = 0; l < nl_; ++l) row_floats_ += dims_[l] * (l >= 1 ? 2 : 1);
-    row_floats_ += dims_[0] + 4;
+    std::vector<int> widths(dims_, dims_ + nl_);                    // act
+    widths.insert(widths.end(), dims_ + 1, dims_ + nl_);            // dzl
+    widths.insert(widths.end(), {dims_[0], 1, 1, 1, 1});            // demb, dz, lrow, brow, z
+    scratch_.init(who, std::move(widths), dims_[0], false);
     sums_ = at::zeros({1}, V.options());
   }
 
@@ -77,24 +81,7 @@ class DeepFMPlan {
   }
 
   // ids > 0 also sizes update()'s scratch
-  void reserve(int64_t B, int64_t ids) {
-    const bool rows_ok = cur_.defined() && cap_ >= B, ids_ok = ids <= 0 || (upd_.defined() && ucap_ >= ids);
-    if (rows_ok && ids_ok) return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    hip_check(hipStreamIsCapturing(cur_stream(), &cs), "DeepFMPlan.reserve");
-    TORCH_CHECK(cs == hipStreamCaptureStatusNone,
-                "DeepFMPlan: the scratch cannot grow inside a stream capture; reserve(rows, ids) before it");
-    if (!rows_ok) {
-      if (cur_.defined()) old_.push_back(cur_);
-      cap_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;      // every part starts 16-byte aligned
-      cur_ = at::empty({cap_ * row_floats_}, V_.options());
-    }
-    if (!ids_ok) {
-      if (upd_.defined()) old_.push_back(upd_);
-      ucap_ = (std::max<int64_t>(ids, 1024) + 1023) / 1024 * 1024;
-      upd_ = at::empty({ucap_ + dtfk_fm_update_part_floats(ucap_, dims_[0])}, V_.options());
-    }
-  }
+  void reserve(int64_t B, int64_t ids) { scratch_.reserve(B, ids, V_.options()); }
 
   // dfm_rows<TM, true> on the current stream for one CSR batch of device tensors;
   // gscale: the loss's scale per row (1 / B for a batch mean).
@@ -134,12 +121,11 @@ class DeepFMPlan {
   void update(at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, int kind, double lr,
               std::vector<at::Tensor> w_slots, std::vector<at::Tensor> V_slots, const py::kwargs& hyper) {
     TORCH_CHECK(B_ > 0, "DeepFMPlan.update: no batch yet (rows() first)");
-    if (fm_update_host("DeepFMPlan.update", w_, V_, B_, offsets, ids, vals, kind, lr, w_slots, V_slots, hyper,
-                       part(2 * nl_), part(2 * nl_ - 1), [&](int64_t N) {
-                         reserve(B_, N);
-                         return std::make_pair(reinterpret_cast<int*>(upd_.data_ptr<float>()),
-                                               upd_.data_ptr<float>() + ucap_);
-                       }))
+    if (table_update_host("DeepFMPlan.update", dtfk_fm_update, w_, V_, B_, offsets, ids, vals, kind, lr, w_slots,
+                          V_slots, c10::nullopt, hyper, part(2 * nl_), part(2 * nl_ - 1), [&](int64_t N, hipStream_t) {
+                            reserve(B_, N);
+                            return UpdateScratch{scratch_.bag_of(), scratch_.update_part(), nullptr};
+                          }))
       ++updates_;
   }
 
@@ -177,8 +163,8 @@ class DeepFMPlan {
   at::Tensor lrow() const { return view(2 * nl_ + 1).reshape({B_}); }
   at::Tensor brow() const { return view(2 * nl_ + 2).reshape({B_}).view(at::kInt); }
   at::Tensor z() const { return view(2 * nl_ + 3).reshape({B_}); }
-  at::Tensor scratch() const { return cur_; }
-  int64_t row_floats() const { return row_floats_; }
+  at::Tensor scratch() const { return scratch_.rows(); }
+  int64_t row_floats() const { return scratch_.row_floats(); }
   int64_t runs() const { return runs_; }
   int64_t updates() const { return updates_; }
   int64_t eval_runs() const { return eval_runs_; }
@@ -196,23 +182,9 @@ class DeepFMPlan {
   void checked(int l, int lo, const char* what) const {
     TORCH_CHECK(l >= lo && l < nl_, "DeepFMPlan.", what, ": layer out of range");
   }
-  // the width of part k of the row scratch, in the order of the list above
-  int part_width(int k) const {
-    if (k < nl_) return dims_[k];
-    if (k < 2 * nl_ - 1) return dims_[k - nl_ + 1];
-    return k == 2 * nl_ - 1 ? dims_[0] : 1;
-  }
-  float* part(int k) const {
-    int64_t off = 0;
-    for (int i = 0; i < k; ++i) off += cap_ * part_width(i);
-    return cur_.data_ptr<float>() + off;
-  }
-  // the last batch's rows of part k: [B, width]
-  at::Tensor view(int k) const {
-    TORCH_CHECK(cur_.defined() && B_ > 0, "DeepFMPlan: no batch yet");
-    const int64_t width = part_width(k);
-    return cur_.narrow(0, part(k) - cur_.data_ptr<float>(), B_ * width).view({B_, width});
-  }
+  // part k of the row scratch, in the order of the list above; view: the last batch's rows of it, [B, width]
+  float* part(int k) const { return scratch_.part(k); }
+  at::Tensor view(int k) const { return scratch_.view(k, B_); }
   // the kernel's view of the tensors and a checked CSR batch (outputs left null)
   dtfk::wde::Args forward_args(const CsrBatch& in) const {
     dtfk::wde::Args a{};
@@ -236,12 +208,13 @@ class DeepFMPlan {
     return a;
   }
 
-  at::Tensor w_, V_, bias_, sums_, cur_, upd_;
-  std::vector<at::Tensor> layers_, old_;
+  at::Tensor w_, V_, bias_, sums_;
+  std::vector<at::Tensor> layers_;
+  StepScratch scratch_;
   EvalScratch eval_{3};
   int dims_[dtfk::wde::MAXL + 1] = {0, 0, 0, 0, 0};
   int nl_ = 0, tile_ = 0;
-  int64_t F_ = 0, cap_ = 0, ucap_ = 0, B_ = 0, row_floats_ = 0;
+  int64_t F_ = 0, B_ = 0;
   int64_t runs_ = 0, updates_ = 0, eval_runs_ = 0;
 };
 

@@ -6,17 +6,18 @@
 // eval_record.hip's reduce.  Every refusal raises before anything is launched; no
 // host read-back and no memset node, so a step can be captured in a hipGraph.
 //
-// Scratch, one tensor of `capacity` rows per part, grown only when a batch exceeds
-// it and never inside a stream capture (an outgrown tensor is kept alive for the
-// graphs that hold it):
+// Scratch (step_scratch.h), one tensor of `capacity` rows per part, grown only when
+// a batch exceeds it and never inside a stream capture (an outgrown tensor is kept
+// alive for the graphs that hold it):
 //   rows:   demb [cap, K] | dz | lrow | brow (int) | z [cap]
-//   update: bag_of [ids cap] (int) | part (fm.h)
+//   update: bag_of [ids cap] (int) | part (table_update.h)
 // An evaluation has per-row arrays of its own (EvalScratch: lrow | prow | brow), so it never disturbs the
 // training step's rows between rows() and update().
 #include "bind_common.h"
 #include "eval_record_host.h"
-#include "fm_update_host.h"
 #include "kernels/fm.h"
+#include "step_scratch.h"
+#include "table_update_host.h"
 #include "kernels/wide_deep_train.h"
 
 #include <algorithm>
@@ -38,29 +39,13 @@ class FMPlan {
     TORCH_CHECK(on_device(w, dev, at::kFloat) && w.numel() == F_, who, ": w must be a contiguous fp32 [F] GPU table on V's device");
     TORCH_CHECK(on_device(bias, dev, at::kFloat) && bias.numel() == 1, who, ": bias must be one fp32 GPU value");
     sums_ = at::zeros({2}, V.options());
+    scratch_.init(who, {(int)K_, 1, 1, 1, 1}, (int)K_, false);
   }
 
   static bool supported(int64_t K) { return K >= 0 && K <= (1 << 20) && dtfk_fm_supported((int)K) == 1; }
 
   // ids > 0 also sizes update()'s scratch
-  void reserve(int64_t B, int64_t ids) {
-    const bool rows_ok = cur_.defined() && cap_ >= B, ids_ok = ids <= 0 || (upd_.defined() && ucap_ >= ids);
-    if (rows_ok && ids_ok) return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    hip_check(hipStreamIsCapturing(cur_stream(), &cs), "FMPlan.reserve");
-    TORCH_CHECK(cs == hipStreamCaptureStatusNone,
-                "FMPlan: the scratch cannot grow inside a stream capture; reserve(rows, ids) before it");
-    if (!rows_ok) {
-      if (cur_.defined()) old_.push_back(cur_);
-      cap_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;      // every part starts 16-byte aligned
-      cur_ = at::empty({cap_ * (K_ + 4)}, V_.options());
-    }
-    if (!ids_ok) {
-      if (upd_.defined()) old_.push_back(upd_);
-      ucap_ = (std::max<int64_t>(ids, 1024) + 1023) / 1024 * 1024;
-      upd_ = at::empty({ucap_ + dtfk_fm_update_part_floats(ucap_, (int)K_)}, V_.options());
-    }
-  }
+  void reserve(int64_t B, int64_t ids) { scratch_.reserve(B, ids, V_.options()); }
 
   // fm_rows<true> on the current stream for one CSR batch of device tensors;
   // gscale: the loss's scale per row (1 / B for a batch mean).
@@ -93,12 +78,11 @@ class FMPlan {
   void update(at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, int kind, double lr,
               std::vector<at::Tensor> w_slots, std::vector<at::Tensor> V_slots, const py::kwargs& hyper) {
     TORCH_CHECK(B_ > 0, "FMPlan.update: no batch yet (rows() first)");
-    if (fm_update_host("FMPlan.update", w_, V_, B_, offsets, ids, vals, kind, lr, w_slots, V_slots, hyper, part(1),
-                       part(0), [&](int64_t N) {
-                         reserve(B_, N);
-                         return std::make_pair(reinterpret_cast<int*>(upd_.data_ptr<float>()),
-                                               upd_.data_ptr<float>() + ucap_);
-                       }))
+    if (table_update_host("FMPlan.update", dtfk_fm_update, w_, V_, B_, offsets, ids, vals, kind, lr, w_slots, V_slots,
+                          c10::nullopt, hyper, part(1), part(0), [&](int64_t N, hipStream_t) {
+                            reserve(B_, N);
+                            return UpdateScratch{scratch_.bag_of(), scratch_.update_part(), nullptr};
+                          }))
       ++updates_;
   }
 
@@ -127,11 +111,11 @@ class FMPlan {
     return pred;
   }
 
-  at::Tensor demb() const { return view(0, K_); }
-  at::Tensor dz() const { return view(1, 1).reshape({B_}); }
-  at::Tensor lrow() const { return view(2, 1).reshape({B_}); }
-  at::Tensor brow() const { return view(3, 1).reshape({B_}).view(at::kInt); }
-  at::Tensor z() const { return view(4, 1).reshape({B_}); }
+  at::Tensor demb() const { return view(0); }
+  at::Tensor dz() const { return view(1).reshape({B_}); }
+  at::Tensor lrow() const { return view(2).reshape({B_}); }
+  at::Tensor brow() const { return view(3).reshape({B_}).view(at::kInt); }
+  at::Tensor z() const { return view(4).reshape({B_}); }
   int64_t runs() const { return runs_; }
   int64_t updates() const { return updates_; }
   int64_t eval_runs() const { return eval_runs_; }
@@ -144,11 +128,8 @@ class FMPlan {
 
  private:
   // part k of the row scratch: demb, dz, lrow, brow, z
-  float* part(int k) const { return cur_.data_ptr<float>() + cap_ * (k == 0 ? 0 : K_ + k - 1); }
-  at::Tensor view(int k, int64_t width) const {
-    TORCH_CHECK(cur_.defined() && B_ > 0, "FMPlan: no batch yet");
-    return cur_.narrow(0, cap_ * (k == 0 ? 0 : K_ + k - 1), B_ * width).view({B_, width});
-  }
+  float* part(int k) const { return scratch_.part(k); }
+  at::Tensor view(int k) const { return scratch_.view(k, B_); }
   dtfk::fm::RowArgs row_args(const CsrBatch& in) const {
     dtfk::fm::RowArgs a{};
     a.w = w_.data_ptr<float>();
@@ -161,17 +142,17 @@ class FMPlan {
     a.offsets = in.offsets;
     a.vals = in.vals;
     a.labels = in.labels;
-    if (cur_.defined()) {                       // the training step's rows; evaluate() puts its own in their place
+    if (scratch_.rows().defined()) {                       // the training step's rows; evaluate() puts its own in their place
       a.lrow = part(2);
       a.brow = reinterpret_cast<int*>(part(3));
     }
     return a;
   }
 
-  at::Tensor w_, V_, bias_, sums_, cur_, upd_;
-  std::vector<at::Tensor> old_;
+  at::Tensor w_, V_, bias_, sums_;
+  StepScratch scratch_;
   EvalScratch eval_{3};
-  int64_t F_ = 0, K_ = 0, cap_ = 0, ucap_ = 0, B_ = 0;
+  int64_t F_ = 0, K_ = 0, B_ = 0;
   int64_t runs_ = 0, updates_ = 0, eval_runs_ = 0;
   int rpw_ = 0;
 };

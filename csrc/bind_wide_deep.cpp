@@ -17,8 +17,9 @@
 // WideDeepTrainPlan.update is the step's table half (csrc/kernels/wide_deep_update.hip
 // wd_update_runs + wd_update_carry): one stable sort of the batch's ids, then every
 // touched row of both tables written once by a row-local rule of optim_rules.h.
-#include "kernels/ops_api.h"
 #include "kernels/wide_deep_update.h"
+#include "step_scratch.h"
+#include "table_update_host.h"
 
 #include <stdexcept>
 #include <string>
@@ -158,8 +159,9 @@ class WideDeepEvalPlan : public WideDeepTensors {
 };
 
 // The per-row half of the one-GPU training step.  The plan owns the step's
-// scratch, one tensor of `capacity` rows per part:
-//   act[0 .. nl-1] [cap, dims[l]] | dzl[1 .. nl-1] [cap, dims[l]] | demb [cap, D] | dz | lrow | brow (int) | z [cap]
+// scratch (step_scratch.h), one tensor of `capacity` rows per part:
+//   rows:   act[0 .. nl-1] [cap, dims[l]] | dzl[1 .. nl-1] [cap, dims[l]] | demb [cap, D] | dz | lrow | brow (int) | z [cap]
+//   update: scale [cap] | bag_of [ids cap] (int) | part (table_update.h)
 // reserve() grows it (never inside a stream capture: a captured graph holds the
 // addresses; an outgrown tensor is kept alive for the graphs that hold it).  The
 // accessors return the last batch's rows of a part.
@@ -169,30 +171,14 @@ class WideDeepTrainPlan : public WideDeepTensors {
                     const std::string& combiner)
       : WideDeepTensors("WideDeepTrainPlan", wide, emb, std::move(layers), bias, combiner) {
     TORCH_CHECK(dtfk_wd_train_supported(dims_[0], nl_, dims_) == 1, "WideDeepTrainPlan: unsupported shape");
-    for (int l = 0; l < nl_; ++l) row_floats_ += dims_[l] * (l >= 1 ? 2 : 1);
-    row_floats_ += dims_[0] + 4;
+    std::vector<int> widths(dims_, dims_ + nl_);                    // act
+    widths.insert(widths.end(), dims_ + 1, dims_ + nl_);            // dzl
+    widths.insert(widths.end(), {dims_[0], 1, 1, 1, 1});            // demb, dz, lrow, brow, z
+    scratch_.init("WideDeepTrainPlan", std::move(widths), dims_[0], true);
   }
 
-  // ids > 0 also sizes update()'s scratch: scale [cap] | bag_of [ids cap] (int) | part (wide_deep_update.h)
-  void reserve(int64_t B, int64_t ids) {
-    const bool rows_ok = cur_.defined() && cap_ >= B, ids_ok = ids <= 0 || (upd_.defined() && ucap_ >= ids && ubag_ >= B);
-    if (rows_ok && ids_ok) return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    hip_check(hipStreamIsCapturing(cur_stream(), &cs), "WideDeepTrainPlan.reserve");
-    TORCH_CHECK(cs == hipStreamCaptureStatusNone,
-                "WideDeepTrainPlan: the scratch cannot grow inside a stream capture; reserve(rows) before it");
-    if (!rows_ok) {
-      if (cur_.defined()) old_.push_back(cur_);
-      cap_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;    // every part starts 16-byte aligned
-      cur_ = at::empty({cap_ * row_floats_}, emb_.options());
-    }
-    if (!ids_ok) {
-      if (upd_.defined()) old_.push_back(upd_);
-      ucap_ = (std::max<int64_t>(ids, 1024) + 1023) / 1024 * 1024;
-      ubag_ = (std::max<int64_t>(B, 1024) + 1023) / 1024 * 1024;
-      upd_ = at::empty({ubag_ + ucap_ + dtfk_wd_update_part_floats(ucap_, dims_[0])}, emb_.options());
-    }
-  }
+  // ids > 0 also sizes update()'s scratch
+  void reserve(int64_t B, int64_t ids) { scratch_.reserve(B, ids, emb_.options()); }
 
   // The rows kernel on the current stream: forward, head and the backward through
   // the tower for one CSR batch of device tensors; gscale: the loss's scale per
@@ -202,19 +188,13 @@ class WideDeepTrainPlan : public WideDeepTensors {
     reserve(in.B, 0);
     dtfk::wdt::Args a{};
     a.f = forward_args(in);
-    int64_t off = 0;
-    auto part = [&](int width) {
-      float* p = cur_.data_ptr<float>() + off;
-      off += cap_ * width;
-      return p;
-    };
-    for (int l = 0; l < nl_; ++l) a.act[l] = part(dims_[l]);
-    for (int l = 1; l < nl_; ++l) a.dzl[l] = part(dims_[l]);
-    a.demb = part(dims_[0]);
-    a.dz = part(1);
-    a.f.lrow = part(1);
-    a.f.brow = reinterpret_cast<int*>(part(1));
-    a.f.z_out = part(1);
+    for (int l = 0; l < nl_; ++l) a.act[l] = scratch_.part(l);
+    for (int l = 1; l < nl_; ++l) a.dzl[l] = scratch_.part(nl_ + l - 1);
+    a.demb = scratch_.part(2 * nl_ - 1);
+    a.dz = scratch_.part(2 * nl_);
+    a.f.lrow = scratch_.part(2 * nl_ + 1);
+    a.f.brow = reinterpret_cast<int*>(scratch_.part(2 * nl_ + 2));
+    a.f.z_out = scratch_.part(2 * nl_ + 3);
     a.gscale = (float)gscale;
     hip_check(dtfk_wd_train_rows(&a, tile_, cur_stream()), "WideDeepTrainPlan: rows kernel");
     B_ = in.B;
@@ -231,9 +211,8 @@ class WideDeepTrainPlan : public WideDeepTensors {
                     dbias.numel() == 1,
                 "WideDeepTrainPlan.sums: db_last / dbias must be one fp32 value each on the plan's GPU");
     at::Tensor loss = at::empty({}, emb_.options());
-    hip_check(dtfk_wd_train_sums(view(nl_ * 2 + 1, 1).data_ptr<float>(), view(nl_ * 2, 1).data_ptr<float>(), (int)B_,
-                                 loss.data_ptr<float>(), db_last.data_ptr<float>(), dbias.data_ptr<float>(),
-                                 cur_stream()),
+    hip_check(dtfk_wd_train_sums(scratch_.part(2 * nl_ + 1), scratch_.part(2 * nl_), (int)B_, loss.data_ptr<float>(),
+                                 db_last.data_ptr<float>(), dbias.data_ptr<float>(), cur_stream()),
               "WideDeepTrainPlan: sums kernel");
     return loss;
   }
@@ -248,78 +227,30 @@ class WideDeepTrainPlan : public WideDeepTensors {
   void update(at::Tensor offsets, at::Tensor ids, c10::optional<at::Tensor> vals, int kind, double lr,
               std::vector<at::Tensor> wide_slots, std::vector<at::Tensor> emb_slots, c10::optional<at::Tensor> skip,
               const py::kwargs& hyper) {
-    const char* who = "WideDeepTrainPlan.update";
-    const int dev = emb_.get_device();
-    TORCH_CHECK(B_ > 0, who, ": no batch yet (rows() first)");
-    TORCH_CHECK(on_device(offsets, dev, at::kLong) && offsets.numel() == B_ + 1, who,
-                ": offsets must be contiguous int64 on the plan's GPU, B + 1 entries of the last rows() batch");
-    TORCH_CHECK(on_device(ids, dev, at::kLong), who, ": ids must be contiguous int64 on the plan's GPU");
-    const int64_t N = ids.numel(), V = emb_.size(0), D = dims_[0];
-    TORCH_CHECK(!vals.has_value() || (on_device(*vals, dev, at::kFloat) && vals->numel() == N), who,
-                ": vals must be contiguous fp32 on the plan's GPU, one per id");
-    TORCH_CHECK(!skip.has_value() || (on_device(*skip, dev, at::kInt) && skip->numel() >= 1), who,
-                ": skip must be a device int32 word");
-    TORCH_CHECK(wide_slots.size() <= 2 && emb_slots.size() == wide_slots.size(), who,
-                ": up to two slots per table, the same number for both");
-    for (size_t i = 0; i < wide_slots.size(); ++i) {
-      TORCH_CHECK(on_device(wide_slots[i], dev, at::kFloat) && wide_slots[i].numel() == V, who,
-                  ": a wide slot must be contiguous fp32 of the table's shape");
-      TORCH_CHECK(on_device(emb_slots[i], dev, at::kFloat) && emb_slots[i].sizes() == emb_.sizes() &&
-                      (reinterpret_cast<uintptr_t>(emb_slots[i].data_ptr()) & 15) == 0,
-                  who, ": an embedding slot must be contiguous fp32 of the table's shape, 16-byte aligned");
-    }
-    dtfk::wdu::Args a{};
-    a.kind = kind;
-    a.h = optim_hyper(lr, hyper);
-    a.D = (int)D;
-    a.V = V;
-    a.N = N;
-    a.wide = wide_.data_ptr<float>();
-    a.emb = emb_.data_ptr<float>();
-    if (wide_slots.size() >= 1) a.wide_a = wide_slots[0].data_ptr<float>(), a.emb_a = emb_slots[0].data_ptr<float>();
-    if (wide_slots.size() >= 2) a.wide_b = wide_slots[1].data_ptr<float>(), a.emb_b = emb_slots[1].data_ptr<float>();
-    // the launcher's refusals, before the sort is launched
-    TORCH_CHECK(dtfk::row_local(kind) && !(dtfk::uses_slot_a(kind) && a.wide_a == nullptr) &&
-                    !(dtfk::uses_slot_b(kind) && a.wide_b == nullptr) &&
-                    !(kind == dtfk::OPT_FTRL && !dtfk::ftrl_hyper_ok(a.h)) && D % 4 == 0 && D >= 4 &&
-                    D <= dtfk::wdu::MAXD && V < (int64_t(1) << 31) && N < (int64_t(1) << 31),
-                who, ": invalid argument (a row-local kind with its slots, FTRL hyper-parameters >= 0, D a multiple "
-                "of 4 in 4 .. 128, fewer than 2^31 table rows and ids)");
-    if (N == 0) return;
-    reserve(B_, N);
-    hipStream_t st = cur_stream();
-    // ids outside the table become -1 / V: the two ends of the sorted order
-    auto sorted = at::sort(at::clamp(ids, -1, V).to(at::kInt), /*stable=*/true, 0, false);
-    const at::Tensor sids = std::get<0>(sorted).contiguous(), perm = std::get<1>(sorted).contiguous();
-    float* scale = upd_.data_ptr<float>();
-    int* bag_of = reinterpret_cast<int*>(scale + ubag_);
-    hip_check(dtfk_bag_index(offsets.data_ptr<int64_t>(), (int)B_, bag_of, N, st), "WideDeepTrainPlan.update: bag_index");
-    if (mode_ != 0)
-      hip_check(dtfk_wd_update_scale(reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()),
-                                     opt_ptr<float>(vals), (int)B_, mode_, scale, st),
-                "WideDeepTrainPlan.update: scale kernel");
-    a.sids = sids.data_ptr<int>();
-    a.perm = reinterpret_cast<const long long*>(perm.data_ptr<int64_t>());
-    a.bag_of = bag_of;
-    a.vals = opt_ptr<float>(vals);
-    a.scale = mode_ != 0 ? scale : nullptr;
-    a.dz = view(2 * nl_, 1).data_ptr<float>();
-    a.demb = view(2 * nl_ - 1, dims_[0]).data_ptr<float>();
-    a.part = scale + ubag_ + ucap_;
-    a.skip = opt_ptr<int>(skip);
-    hip_check(dtfk_wd_update(&a, st), "WideDeepTrainPlan.update");
-    ++updates_;
+    TORCH_CHECK(B_ > 0, "WideDeepTrainPlan.update: no batch yet (rows() first)");
+    if (table_update_host("WideDeepTrainPlan.update", dtfk_wd_update, wide_, emb_, B_, offsets, ids, vals, kind, lr,
+                          wide_slots, emb_slots, skip, hyper, scratch_.part(2 * nl_), scratch_.part(2 * nl_ - 1),
+                          [&](int64_t N, hipStream_t st) {
+                            reserve(B_, N);
+                            if (mode_ != 0)
+                              hip_check(dtfk_wd_update_scale(reinterpret_cast<const long long*>(offsets.data_ptr<int64_t>()),
+                                                             opt_ptr<float>(vals), (int)B_, mode_, scratch_.scale(), st),
+                                        "WideDeepTrainPlan.update: scale kernel");
+                            return UpdateScratch{scratch_.bag_of(), scratch_.update_part(),
+                                                 mode_ != 0 ? scratch_.scale() : nullptr};
+                          }))
+      ++updates_;
   }
 
-  at::Tensor act(int l) const { return checked(l, 0, "act"), view(l, dims_[l]); }
-  at::Tensor dzl(int l) const { return checked(l, 1, "dzl"), view(nl_ + l - 1, dims_[l]); }
-  at::Tensor demb() const { return view(2 * nl_ - 1, dims_[0]); }
-  at::Tensor dz() const { return view(2 * nl_, 1); }
-  at::Tensor lrow() const { return view(2 * nl_ + 1, 1).reshape({B_}); }
-  at::Tensor brow() const { return view(2 * nl_ + 2, 1).reshape({B_}).view(at::kInt); }
-  at::Tensor z() const { return view(2 * nl_ + 3, 1).reshape({B_}); }
-  at::Tensor scratch() const { return cur_; }
-  int64_t row_floats() const { return row_floats_; }
+  at::Tensor act(int l) const { return checked(l, 0, "act"), view(l); }
+  at::Tensor dzl(int l) const { return checked(l, 1, "dzl"), view(nl_ + l - 1); }
+  at::Tensor demb() const { return view(2 * nl_ - 1); }
+  at::Tensor dz() const { return view(2 * nl_); }
+  at::Tensor lrow() const { return view(2 * nl_ + 1).reshape({B_}); }
+  at::Tensor brow() const { return view(2 * nl_ + 2).reshape({B_}).view(at::kInt); }
+  at::Tensor z() const { return view(2 * nl_ + 3).reshape({B_}); }
+  at::Tensor scratch() const { return scratch_.rows(); }
+  int64_t row_floats() const { return scratch_.row_floats(); }
   int64_t runs() const { return runs_; }
   int64_t updates() const { return updates_; }
   void set_tile(int tile) {
@@ -334,22 +265,10 @@ class WideDeepTrainPlan : public WideDeepTensors {
     TORCH_CHECK(l >= lo && l < nl_, "WideDeepTrainPlan.", what, ": layer out of range");
   }
   // part k of the scratch in rows()'s order, the last batch's rows: [B, width]
-  at::Tensor view(int k, int width) const {
-    TORCH_CHECK(cur_.defined() && B_ > 0, "WideDeepTrainPlan: no batch yet");
-    int64_t off = 0;
-    for (int i = 0; i < k; ++i) off += cap_ * part_width(i);
-    return cur_.narrow(0, off, B_ * width).view({B_, width});
-  }
-  int part_width(int i) const {
-    if (i < nl_) return dims_[i];
-    if (i < 2 * nl_ - 1) return dims_[i - nl_ + 1];
-    return i == 2 * nl_ - 1 ? dims_[0] : 1;
-  }
+  at::Tensor view(int k) const { return scratch_.view(k, B_); }
 
-  at::Tensor cur_, upd_;
-  std::vector<at::Tensor> old_;
-  int64_t cap_ = 0, B_ = 0, row_floats_ = 0, runs_ = 0;
-  int64_t ucap_ = 0, ubag_ = 0, updates_ = 0;
+  StepScratch scratch_;
+  int64_t B_ = 0, runs_ = 0, updates_ = 0;
   int tile_ = 0;
 };
 

@@ -2,16 +2,15 @@
 // (Rendle 2010) on one GPU.  fm_rows scores a CSR batch (and, training, leaves the
 // bag gradients); fm_update_runs + fm_update_carry write every touched row of the
 // linear table w [F] and the factor table V [F, K] once, by a row-local rule of
-// optim_rules.h.
+// optim_rules.h (the args and the scheme: table_update.h).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include "optim_rules.h"
+#include "table_update.h"
 
 namespace dtfk {
 namespace fm {
 
-constexpr int CHUNK = 64;     // sorted positions per wave of the update
 constexpr int MAXK = 128;
 constexpr int MAXRPW = 64;    // rows per wave of fm_rows: one lane holds each row's offsets
 
@@ -36,21 +35,6 @@ struct RowArgs {
   float gscale;
 };
 
-struct UpdArgs {
-  const int* sids;            // [N] the ids in ascending order (stable sort); outside [0, F): no part in anything
-  const long long* perm;      // [N] the CSR position of each sorted position
-  const int* bag_of;          // [N] the row of each CSR position
-  const float* vals;          // [N] by CSR position, or null: every value is 1
-  const float* dz;            // [B]
-  const float* demb;          // [B, K]
-  float *w, *w_a, *w_b;       // [F] table and its slots (null where the kind has none)
-  float *V, *V_a, *V_b;       // [F, K], 16-byte aligned
-  float* part;                // [chunks, 2, K + 4]: a chunk's leading / trailing partials (columns, w's sum, q)
-  long long N, F;
-  int K, kind;
-  OptimHyper h;
-};
-
 }  // namespace fm
 }  // namespace dtfk
 
@@ -62,9 +46,7 @@ int dtfk_fm_rpw(int B);
 // fm_rows on `stream`; train != 0 also writes dz and demb.  rpw: rows per wave, 1 .. 64, or 0 (automatic).
 // hipErrorInvalidValue before any launch: an unsupported K, a missing or misaligned pointer, B < 1, F < 1.
 hipError_t dtfk_fm_rows(const dtfk::fm::RowArgs* a, int train, int rpw, hipStream_t stream);
-// Floats of UpdArgs::part for N ids.
-long long dtfk_fm_update_part_floats(long long N, int K);
-// fm_update_runs, then fm_update_carry, on `stream`.  hipErrorInvalidValue before any launch: a kind that is
-// not row-local, a missing slot, FTRL hyper-parameters out of range, an unsupported K, F >= 2^31 or N >= 2^31.
-hipError_t dtfk_fm_update(const dtfk::fm::UpdArgs* a, hipStream_t stream);
+// fm_update_runs, then fm_update_carry, on `stream`: table_update.h's FM form, Args::lin = w, Args::row = V.
+// hipErrorInvalidValue before any launch: what table_update.h's check refuses.
+hipError_t dtfk_fm_update(const dtfk::tu::Args* a, hipStream_t stream);
 }

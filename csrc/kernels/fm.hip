@@ -25,13 +25,8 @@
 //   dL/dw[j]    = sum_{occ of j} x dz_r
 //   dL/dV[j, f] = sum_{occ of j} x demb[r, f]  -  V[j, f] q_j,     q_j = sum_{occ of j} x^2 dz_r
 //
-// fm_update_runs / fm_update_carry: the one-writer scheme of wide_deep_update.hip
-// (ids sorted once, a wave per 64 sorted positions, runs summed by a segmented
-// scan in a fixed order, a run over a chunk edge folded by the carry kernel from
-// per-chunk partials; no atomics, the same bits on every run).  Here a run also
-// carries q (a partial is K + 2 floats in a stride of K + 4), and the writer
-// forms  g[f] = sum[f] - V_old[j, f] q  from the row it has just loaded, before
-// the rule of optim_rules.h.
+// fm_update_runs / fm_update_carry: the FM form of table_update.h's one-writer
+// scheme (described there), w as the linear table and V as the row table.
 #include "common.h"
 #include "fm.h"
 
@@ -40,9 +35,6 @@ namespace fm {
 
 constexpr int WAVES = 4;
 constexpr int GS = 16;                          // table-row loads in flight per lane (fm_rows)
-constexpr int PASSES = 4;                       // gathered demb rows in flight per lane (fm_update_runs)
-
-__host__ __device__ constexpr int part_stride(int K) { return K + 4; }   // columns, w's sum, q, padding to 16 bytes
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -178,179 +170,8 @@ __global__ __launch_bounds__(64 * WAVES) void fm_rows(const RowArgs a, const int
 
 // ---------------------------------------------------------------- the table update
 
-// the head of the run that position q (0 .. 63) lies in
-__device__ __forceinline__ int run_start(unsigned long long heads, int q) {
-  return 63 - __clzll((long long)(heads & (~0ull >> (63 - q))));
-}
-
-// where the sum of the run [start, q] of a chunk goes: -1 = applied here, else the slot of `part`
-__device__ __forceinline__ int run_slot(int start, int q, bool lead, bool trail) {
-  if (start == 0 && (lead || (trail && q == 63))) return 0;
-  return trail && q == 63 ? 1 : -1;
-}
-
-// four columns of a factor row: g = s - V_old qrun, then the rule
-__device__ __forceinline__ void apply_factors(const UpdArgs& a, size_t o, f32x4 s, float qrun) {
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4 var = *reinterpret_cast<const f32x4*>(a.V + o);
-  f32x4 sa = a.V_a != nullptr ? *reinterpret_cast<const f32x4*>(a.V_a + o) : zero;
-  f32x4 sb = a.V_b != nullptr ? *reinterpret_cast<const f32x4*>(a.V_b + o) : zero;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float v1 = var[k], a1 = sa[k], b1 = sb[k];
-    update1(v1, a1, b1, s[k] - v1 * qrun, a.kind, a.h);
-    var[k] = v1; sa[k] = a1; sb[k] = b1;
-  }
-  *reinterpret_cast<f32x4*>(a.V + o) = var;
-  if (a.V_a != nullptr) *reinterpret_cast<f32x4*>(a.V_a + o) = sa;
-  if (a.V_b != nullptr) *reinterpret_cast<f32x4*>(a.V_b + o) = sb;
-}
-
-__device__ __forceinline__ void apply_linear(const UpdArgs& a, size_t o, float g) {
-  float var = a.w[o], sa = a.w_a != nullptr ? a.w_a[o] : 0.f, sb = a.w_b != nullptr ? a.w_b[o] : 0.f;
-  update1(var, sa, sb, g, a.kind, a.h);
-  a.w[o] = var;
-  if (a.w_a != nullptr) a.w_a[o] = sa;
-  if (a.w_b != nullptr) a.w_b[o] = sb;
-}
-
-__global__ __launch_bounds__(64 * WAVES) void fm_update_runs(const UpdArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long long c = (long long)blockIdx.x * WAVES + uni((int)(threadIdx.x >> 6));
-  const long long p0 = c * CHUNK;
-  if (p0 >= a.N) return;
-  const int cnt = (int)(a.N - p0 < CHUNK ? a.N - p0 : CHUNK);
-  const int K = a.K, PS = part_stride(K);
-
-  // this lane's occurrence; row < 0: past the batch or an id outside the table
-  int row = -1, b = 0;
-  float x = 0.f;
-  if (lane < cnt) {
-    const int id = a.sids[p0 + lane];
-    if (id >= 0 && id < a.F) {
-      const long long j = a.perm[p0 + lane];
-      row = id;
-      b = a.bag_of[j];
-      x = a.vals != nullptr ? a.vals[j] : 1.f;
-    }
-  }
-  const int prev = __shfl_up(row, 1, 64);
-  const unsigned long long heads = __ballot(lane == 0 || prev != row);
-  const unsigned long long tails = (heads >> 1) | (1ull << 63);
-  const int first = __shfl(row, 0, 64), last = __shfl(row, 63, 64);
-  // the first run goes on from the previous chunk / the last one into the next
-  const bool lead = first >= 0 && c > 0 && a.sids[p0 - 1] == first;
-  const bool trail = last >= 0 && p0 + CHUNK < a.N && a.sids[p0 + CHUNK] == last;
-  float* __restrict__ part = a.part + (size_t)c * 2 * PS;
-
-  // ---- linear table and q: lanes own occurrences, one segmented scan for both sums
-  float qs;
-  {
-    const float d = a.dz[b];
-    float v = x * d;
-    qs = (x * x) * d;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float vu = __shfl_up(v, off, 64), qu = __shfl_up(qs, off, 64);
-      const int ru = __shfl_up(row, off, 64);
-      if (lane >= off && ru == row) {
-        v += vu;
-        qs += qu;
-      }
-    }
-    if (row >= 0 && ((tails >> lane) & 1)) {
-      const int slot = run_slot(run_start(heads, lane), lane, lead, trail);
-      if (slot >= 0) {
-        part[slot * PS + K] = v;
-        part[slot * PS + K + 1] = qs;
-      } else {
-        apply_linear(a, (size_t)row, v);
-      }
-    }
-  }
-
-  // ---- factor table: lanes across columns, R positions per pass
-  const int G = K >> 2, R = 64 / G;
-  const int g = lane / G, col = (lane - g * G) * 4;
-  const bool live = g < R;
-  const int carry_src = (R - 1) * G + (lane - g * G);
-  f32x4 carry = {0.f, 0.f, 0.f, 0.f};
-  for (int q0 = 0; q0 < cnt; q0 += PASSES * R) {
-    f32x4 v[PASSES];
-    int rq[PASSES];
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {                 // no branch: every lane shuffles and loads in every pass
-      const int q = q0 + u * R + g, qc = q < 63 ? q : 63;
-      const int bq = __shfl(b, qc, 64), rowq = __shfl(row, qc, 64);
-      const float xq = __shfl(x, qc, 64);
-      const bool on = live && q < 64;                  // else: a clamped address, times 0
-      rq[u] = on ? rowq : -1;
-      v[u] = (on ? xq : 0.f) * *reinterpret_cast<const f32x4*>(a.demb + (size_t)bq * K + col);
-    }
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int base = q0 + u * R;
-      if (base >= cnt) break;                          // wave-uniform
-      const int q = base + g, qc = q < 63 ? q : 63;
-      const int st = run_start(heads, qc);
-      const float qrun = __shfl(qs, qc, 64);           // q of the run [st, q]
-      f32x4 s = v[u];
-      for (int off = 1; off < R; off <<= 1) {          // segmented scan over the pass's groups
-        f32x4 up;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) up[k] = __shfl_up(s[k], off * G, 64);
-        if (g >= off && st <= q - off) s += up;
-      }
-      if (st < base) s += carry;                       // the run began in an earlier pass
-#pragma unroll
-      for (int k = 0; k < 4; ++k) carry[k] = __shfl(s[k], carry_src, 64);
-      if (rq[u] >= 0 && ((tails >> qc) & 1)) {
-        const int slot = run_slot(st, q, lead, trail);
-        if (slot >= 0) *reinterpret_cast<f32x4*>(part + slot * PS + col) = s;
-        else apply_factors(a, (size_t)rq[u] * K + col, s, qrun);
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(64 * WAVES) void fm_update_carry(const UpdArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long long c = (long long)blockIdx.x * WAVES + uni((int)(threadIdx.x >> 6));
-  const long long p0 = c * CHUNK;
-  if (p0 + CHUNK >= a.N) return;                       // no next chunk: nothing goes on
-  const int id = a.sids[p0 + CHUNK - 1];
-  if (id < 0 || id >= a.F || a.sids[p0 + CHUNK] != id) return;
-  if (c > 0 && a.sids[p0 - 1] == id) return;           // the run started in an earlier chunk: that wave folds it
-  const int K = a.K, G = K >> 2, PS = part_stride(K);
-  const long long nch = (a.N + CHUNK - 1) / CHUNK;
-  // lanes < G: 4 columns each; lane G: w's sum and q
-  const bool cols = lane < G, lin = lane == G;
-  const float* __restrict__ part = a.part;
-  const int slot = a.sids[p0] == id ? 0 : 1;           // a run that covers the whole chunk wrote the leading slot
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float accw = 0.f, accq = 0.f;
-  {
-    const float* p = part + (size_t)(c * 2 + slot) * PS;
-    if (cols) acc = *reinterpret_cast<const f32x4*>(p + lane * 4);
-    if (lin) accw = p[K], accq = p[K + 1];
-  }
-  for (long long k = c + 1; k < nch; k += 64) {
-    // the next 64 chunk starts at once: the run goes on through the first n of them
-    const long long kk = k + lane;
-    const unsigned long long hit = __ballot(kk < nch && a.sids[kk * CHUNK] == id);
-    const int n = ~hit == 0ull ? 64 : __ffsll((long long)~hit) - 1;
-#pragma unroll 4
-    for (int i = 0; i < n; ++i) {
-      const float* p = part + (size_t)(k + i) * 2 * PS;
-      if (cols) acc += *reinterpret_cast<const f32x4*>(p + lane * 4);
-      if (lin) accw += p[K], accq += p[K + 1];
-    }
-    if (n < 64) break;
-  }
-  const float qrun = __shfl(accq, G, 64);
-  if (cols) apply_factors(a, (size_t)id * K + lane * 4, acc, qrun);
-  if (lin) apply_linear(a, (size_t)id, accw);
-}
+__global__ __launch_bounds__(64 * WAVES) void fm_update_runs(const tu::Args a) { tu::update_runs<true>(a); }
+__global__ __launch_bounds__(64 * WAVES) void fm_update_carry(const tu::Args a) { tu::update_carry<true>(a); }
 
 }  // namespace fm
 }  // namespace dtfk
@@ -387,31 +208,6 @@ extern "C" hipError_t dtfk_fm_rows(const dtfk::fm::RowArgs* a, int train, int rp
   return hipGetLastError();
 }
 
-extern "C" long long dtfk_fm_update_part_floats(long long N, int K) {
-  return (N + dtfk::fm::CHUNK - 1) / dtfk::fm::CHUNK * 2 * dtfk::fm::part_stride(K);
-}
-
-extern "C" hipError_t dtfk_fm_update(const dtfk::fm::UpdArgs* a, hipStream_t stream) {
-  using namespace dtfk;
-  using namespace dtfk::fm;
-  if (a == nullptr || !row_local(a->kind)) return hipErrorInvalidValue;
-  if (uses_slot_a(a->kind) && (a->w_a == nullptr || a->V_a == nullptr)) return hipErrorInvalidValue;
-  if (uses_slot_b(a->kind) && (a->w_b == nullptr || a->V_b == nullptr)) return hipErrorInvalidValue;
-  if (a->kind == OPT_FTRL && !ftrl_hyper_ok(a->h)) return hipErrorInvalidValue;
-  if (!dtfk_fm_supported(a->K)) return hipErrorInvalidValue;
-  if (a->F < 1 || a->F >= (1ll << 31) || a->N < 0 || a->N >= (1ll << 31)) return hipErrorInvalidValue;
-  if (a->N == 0) return hipSuccess;
-  if (a->sids == nullptr || a->perm == nullptr || a->bag_of == nullptr || a->dz == nullptr || a->demb == nullptr ||
-      a->w == nullptr || a->V == nullptr || a->part == nullptr)
-    return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(a->V) | reinterpret_cast<uintptr_t>(a->V_a) | reinterpret_cast<uintptr_t>(a->V_b) |
-       reinterpret_cast<uintptr_t>(a->demb) | reinterpret_cast<uintptr_t>(a->part)) & 15)
-    return hipErrorInvalidValue;
-  const long long chunks = (a->N + CHUNK - 1) / CHUNK;
-  const dim3 grid((unsigned)((chunks + WAVES - 1) / WAVES)), block(64 * WAVES);
-  hipLaunchKernelGGL(fm_update_runs, grid, block, 0, stream, *a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || chunks == 1) return e;
-  hipLaunchKernelGGL(fm_update_carry, grid, block, 0, stream, *a);
-  return hipGetLastError();
+extern "C" hipError_t dtfk_fm_update(const dtfk::tu::Args* a, hipStream_t stream) {
+  return dtfk::tu::launch(a, stream, dtfk::fm::fm_update_runs, dtfk::fm::fm_update_carry);
 }
