@@ -1,4 +1,4 @@
-// Reached by: WideDeepTrainPlan.update (csrc/bind_wide_deep.cpp), WideDeep(fused_step="combined"); tests/test_wide_deep_update_gpu.py
+// Reached by: WideDeepTrainPlan.update (csrc/bind_wide_deep.cpp), WideDeep(fused_step="combined"), FFMPlan.update (csrc/bind_ffm.cpp: B P bags of width P K); tests/test_wide_deep_update_gpu.py
 // The table update of the one-GPU Wide&Deep training step: table_update.h's
 // one-writer scheme (described there) on the wide table [V, 1] and the embedding
 // table [V, D], an occurrence weighted by its value and the combiner's scale of

@@ -1,5 +1,5 @@
 // The scratch of a one-GPU training step's plan (bind_fm.cpp FMPlan, bind_deepfm.cpp
-// DeepFMPlan, bind_wide_deep.cpp WideDeepTrainPlan): two tensors that grow only
+// DeepFMPlan, bind_ffm.cpp FFMPlan, bind_wide_deep.cpp WideDeepTrainPlan): two tensors that grow only
 // when a batch exceeds them and never inside a stream capture (a captured graph
 // holds the addresses; an outgrown tensor is kept alive for the graphs that hold it).
 //   rows:   one part of [capacity, width] floats per entry of `widths`, after each other

@@ -1,6 +1,6 @@
 // The table half of a training step that ends in kernels/table_update.h's one-writer
-// update, as FMPlan.update (bind_fm.cpp), DeepFMPlan.update (bind_deepfm.cpp) and
-// WideDeepTrainPlan.update (bind_wide_deep.cpp) run it: the checks, one stable sort
+// update, as FMPlan.update (bind_fm.cpp), DeepFMPlan.update (bind_deepfm.cpp),
+// FFMPlan.update (bind_ffm.cpp) and WideDeepTrainPlan.update (bind_wide_deep.cpp) run it: the checks, one stable sort
 // of the batch's ids, bag_index, then the file's launcher (dtfk_fm_update /
 // dtfk_wd_update) with the plan's dz / demb.  `who` prefixes the messages; every
 // refusal raises before anything is launched.

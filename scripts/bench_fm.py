@@ -1,6 +1,6 @@
 """Cost of a factorization-machine training step and evaluation on one GPU, through FMTrainer's public interface:
 
-    python scripts/bench_fm.py [--features 100000000] [--rounds 3] [--out FILE] [--hidden 512,256]
+    python scripts/bench_fm.py [--features 100000000] [--rounds 3] [--out FILE] [--hidden 512,256] [--fields 22]
 
 F = 1e8 features, K = 64 factors, about 40 ids per row (Zipf-hot), SGD, device-resident batches of 500 and 4096
 rows.  Two variants, measured in alternating fresh child processes, `--rounds` each: the fused path
@@ -17,6 +17,11 @@ JSON document.
 --hidden W1,W2,..: the same for DeepFM (models/deepfm.py DeepFMTrainer with that tower, csrc/kernels/deepfm.hip):
 its fused path against its torch path (DTF_DFM_FUSED=0, the baseline: there was no DeepFM before), and the plain
 fused FM step next to both; no rows-per-wave sweep.  The record then also lists every run of every variant.
+
+--fields P: the same for the field-aware FM (models/ffm.py FFMTrainer with P fields of K = 4 factors,
+csrc/kernels/ffm.hip): one entry per field and row (Zipf-hot ids), the batch in the (row, field) bag form; its fused
+path against its torch path (DTF_FFM_FUSED=0, the baseline: there was no FFM before); no rows-per-wave sweep, and the
+record lists every run.
 
 What a step must move at B = 4096: 4096 x 40 table rows x 256 B = 42 MB of random 256-byte reads in fm_rows, and
 per distinct id one 256-byte read and write in the update.
@@ -42,6 +47,14 @@ def _batch(rng, B, F, per=40):
     return ((rng.random(B) < 0.3).astype(np.float32), off, ids, rng.uniform(0.5, 1.5, n).astype(np.float32))
 
 
+def _ffm_batch(rng, B, F, P):
+    """One entry per (row, field) bag."""
+    n = B * P
+    ids = np.minimum(rng.zipf(1.2, n) - 1, F - 1).astype(np.int64)
+    return ((rng.random(B) < 0.3).astype(np.float32), np.arange(n + 1, dtype=np.int64), ids,
+            rng.uniform(0.5, 1.5, n).astype(np.float32))
+
+
 def _stream_ms(torch, fn, reps=20, warmup=5, inner=10):
     for _ in range(warmup):
         fn()
@@ -58,28 +71,31 @@ def _stream_ms(torch, fn, reps=20, warmup=5, inner=10):
     return float(np.median(out))
 
 
-def worker(tree, F, hidden=()):
+def worker(tree, F, hidden=(), fields=0):
     sys.path.insert(0, tree)
     import torch
 
-    from distributed_tensorflow_example_amd.models import DeepFMTrainer, FMTrainer
+    from distributed_tensorflow_example_amd.models import DeepFMTrainer, FFMTrainer, FMTrainer
     from distributed_tensorflow_example_amd.parallel.world import World
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     rng = np.random.default_rng(0)
-    if hidden:
+    if fields:
+        m = FFMTrainer(F, num_fields=fields, factors=4, lr=0.05, world=World(device=dev))
+    elif hidden:
         m = DeepFMTrainer(F, factors=64, hidden=hidden, lr=0.05, world=World(device=dev))
     else:
         m = FMTrainer(F, factors=64, lr=0.05, world=World(device=dev))
     res = {"fused": bool(m._fused_ok())}
-    batches = {B: tuple(torch.from_numpy(a).to(dev) for a in _batch(rng, B, F)) for B in (500, 4096)}
+    batches = {B: tuple(torch.from_numpy(a).to(dev) for a in (_ffm_batch(rng, B, F, fields) if fields else _batch(rng, B, F)))
+               for B in (500, 4096)}
     for B, b in batches.items():
         res[f"train_step_eager_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.train_step(b))
         res[f"evaluate_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.evaluate(b))
     if res["fused"]:
         plan = m._native_plan()
-        for B, b in ({} if hidden else batches).items():
+        for B, b in ({} if hidden or fields else batches).items():
             res[f"rpw_auto_{B}"] = int(plan.rpw_for(B))
             for r in RPWS:
                 plan.set_rpw(r)
@@ -100,21 +116,24 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--worker", default="")
     ap.add_argument("--hidden", default="", help="DeepFM's hidden widths, e.g. 512,256 (default: the plain FM)")
+    ap.add_argument("--fields", type=int, default=0, help="the field-aware FM with this many fields of 4 factors")
     a = ap.parse_args()
     if a.worker:
-        return worker(a.worker, a.features, tuple(int(h) for h in a.hidden.split(",") if h))
+        return worker(a.worker, a.features, tuple(int(h) for h in a.hidden.split(",") if h), a.fields)
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     variants = [("fused", {"DTF_FM_FUSED": "1"}, ""), ("general_path", {"DTF_FM_FUSED": "0"}, "")]
     if a.hidden:
         variants = [("fused", {"DTF_DFM_FUSED": "1"}, a.hidden), ("general_path", {"DTF_DFM_FUSED": "0"}, a.hidden),
                     ("fm_fused", {"DTF_FM_FUSED": "1"}, "")]
+    if a.fields:
+        variants = [("fused", {"DTF_FFM_FUSED": "1"}, ""), ("general_path", {"DTF_FFM_FUSED": "0"}, "")]
     runs = {name: [] for name, _, _ in variants}
     for r in range(a.rounds):
         # alternating: one process per variant per round, the order reversed every other round
         for name, env, hidden in (variants if r % 2 == 0 else variants[::-1]):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", here, "--features",
-                                str(a.features), "--hidden", hidden], capture_output=True, text=True, env=dict(os.environ, **env),
-                               timeout=300)
+                                str(a.features), "--hidden", hidden, "--fields", str(a.fields)], capture_output=True,
+                               text=True, env=dict(os.environ, **env), timeout=300)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
             if p.returncode != 0 or not line:
                 raise SystemExit(f"{name} round {r} failed:\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
@@ -136,7 +155,10 @@ def main():
     out["general_over_fused"] = {k: round(g[k]["median"] / f[k]["median"], 2) for k in g if k.endswith("_ms")}
     # faster by more than the spread: the fused path's slowest run under the general path's fastest
     out["fused_faster_beyond_spread"] = {k: bool(f[k]["max"] < g[k]["min"]) for k in g if k.endswith("_ms")}
-    if a.hidden:
+    if a.fields:
+        out.update(fields=a.fields, factors=4, ids_per_row=a.fields, table_row_bytes_read_by_fm_rows_at_4096=4096 * a.fields ** 2 * 16)
+        out["runs"] = {name: {k: [x[k] for x in rs] for k in rs[0] if k.endswith("_ms")} for name, rs in runs.items()}
+    elif a.hidden:
         out["hidden"] = [int(h) for h in a.hidden.split(",")]
         fm = out["variants"]["fm_fused"]
         out["fused_over_fm_fused"] = {k: round(f[k]["median"] / fm[k]["median"], 2) for k in f if k.endswith("_ms") and k in fm}
