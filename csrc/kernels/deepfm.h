@@ -3,7 +3,9 @@
 // dfm_rows scores a CSR batch and, training, leaves the tower's activations and
 // gradients and the bag gradient demb = dz S + da_0; the table update is fm.h's
 // (dtfk_fm_update, with this kernel's dz and demb), the sums wide_deep_train.h's
-// and the evaluation's reduce eval_record.h's.
+// and the evaluation's reduce eval_record.h's.  This is the form without fields (the
+// tower reads the pooled S); the form whose tower reads the concatenated per-field
+// embeddings is deepfm_fields.h.
 //
 // The argument struct is wide_deep_train.h's wdt::Args:  f.Wt = w [F], f.E = V [F, K],
 // f.D = K, f.mode = 0 (sum: there is no combiner scale), the tower in f.W / f.b /

@@ -1,8 +1,10 @@
 // Reached by: DeepFMPlan (csrc/bind_deepfm.cpp), models/deepfm.py DeepFMTrainer; tests/test_deepfm_gpu.py, scripts/bench_fm.py --hidden
 // DeepFM (Guo et al. 2017) on one GPU: a factorization machine and an MLP tower
-// that read the same factor table.  The batches are CSR rows without fields, so the
-// tower reads the pooled factors S_r (as wide_deep's tower reads its sum-combined
-// bag), not a concatenation of per-field embeddings.
+// that read the same factor table.  This file is the form without fields: the
+// batches are CSR rows and the tower reads the pooled factors S_r (as wide_deep's
+// tower reads its sum-combined bag).  The form with fields, whose tower reads the
+// concatenation of the per-field embeddings as the paper's does, is
+// deepfm_fields.hip (dfmf_rows, over the (row, field) bag form).
 //
 //   S_r[f] = sum_i x_i V[id_i, f]        Q_r[f] = sum_i x_i^2 V[id_i, f]^2
 //   fm_r   = sum_i x_i w[id_i] + 0.5 sum_f (S_r[f]^2 - Q_r[f])

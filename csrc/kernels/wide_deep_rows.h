@@ -1,8 +1,9 @@
 // Device code that the tower row kernels share (wide_deep_eval.hip wd_eval_rows,
-// wide_deep_train.hip wd_train_rows, deepfm.hip dfm_rows): the exact-fp32 MFMA
+// wide_deep_train.hip wd_train_rows, deepfm.hip dfm_rows, deepfm_fields.hip
+// dfmf_rows): the exact-fp32 MFMA
 // hidden layer with its four-deep operand ring, its backward (layer_bwd: described
 // in wide_deep_train.hip's header) and the bag reader's helpers (the Wide&Deep
-// reader itself: wide_deep_bags.h).  Included by those three .hip files only, after
+// reader itself: wide_deep_bags.h).  Included by those four .hip files only, after
 // common.h and wide_deep_eval.h; the designs are described in wide_deep_eval.hip's
 // and wide_deep_train.hip's headers.
 #pragma once
@@ -146,11 +147,14 @@ __device__ __forceinline__ void mma_block_t(f32x4 (&acc)[4], const float4 av, co
 //   FMS (deepfm.hip, with FIRST): the table is shared with a factorization machine,
 //     demb = da + dz_s[row] gact[row][:], where gact is the tile's act[0] = S rows in
 //     global memory and dz_s the tile's dz in LDS (rows >= `rows`: row rows - 1's, not stored).
-template <int TM, bool FIRST, bool GMASK, bool FMS = false>
+//   FIELDS (deepfm_fields.hip, with FMS): da is P blocks of fk columns, one per field, and every
+//     block takes the same dz S: gact is the tile's S [TM][fk] in LDS, read at column col mod fk
+//     (fk % 4 == 0: a 16-byte column group lies inside one field).
+template <int TM, bool FIRST, bool GMASK, bool FMS = false, bool FIELDS = false>
 __device__ __forceinline__ void layer_bwd(const float* __restrict__ G, int ldg, float* out, int ldo,
                                           const float* __restrict__ W, int K, int N, int w, int lane,
                                           const float* gact, float* __restrict__ gout, int rows,
-                                          const float* dz_s = nullptr) {
+                                          const float* dz_s = nullptr, int fk = 0) {
   const int r = lane & 15, g = lane >> 4;
   const int nnb = N >> 4, nch = (K + 63) >> 6, items = (TM / 16) * nch;
   for (int it = w; it < items; it += NW) {
@@ -201,7 +205,9 @@ __device__ __forceinline__ void layer_bwd(const float* __restrict__ G, int ldg, 
           *reinterpret_cast<float4*>(op) = v;
         }
         if constexpr (FMS) {
-          const float4 sv = *reinterpret_cast<const float4*>(gact + (size_t)min(row, rows - 1) * K + col);
+          float4 sv;
+          if constexpr (FIELDS) sv = *reinterpret_cast<const float4*>(gact + row * fk + col % fk);
+          else sv = *reinterpret_cast<const float4*>(gact + (size_t)min(row, rows - 1) * K + col);
           const float d = dz_s[row];
           v.x += d * sv.x;
           v.y += d * sv.y;

@@ -1,9 +1,16 @@
 """DeepFM (Guo et al. 2017) on libsvm / CTR batches: a factorization machine and an MLP tower
 that read the same factor table.
 
-The batches here are CSR rows without fields, so the tower reads the pooled factors S_r (as
-models/wide_deep.py's tower reads its sum-combined bag); the paper concatenates per-field
-embeddings instead.
+Two forms.  Without fields (num_fields None) the batches are CSR rows, and the tower reads the
+pooled factors S_r (as models/wide_deep.py's tower reads its sum-combined bag).  With
+num_fields = P the batches are models/ffm.py's bag form (labels [B], offsets [B * P + 1], ids,
+vals; `ffm_batch` makes it from a field per entry), entries of one bag are sum-pooled, and the
+tower reads the concatenation of the P per-field embeddings, as the paper's does:
+
+    A_r[p] = sum_{i in bag (r, p)} x_i V[id_i, :]       a_0 = [A_r[0] | ... | A_r[P-1]]   (P * K wide)
+    demb[r P + p, :] = dz_r S_r + da_0,r[p K : (p + 1) K]     dL/dV[j,f] = sum_occ x demb[bag_occ, f] - V[j,f] q_j
+
+with S, Q and the FM term over all of the row's entries, as without fields:
 
     S_r[f] = sum_i x_i V[id_i, f]        Q_r[f] = sum_i x_i^2 V[id_i, f]^2
     fm_r   = sum_i x_i w[id_i] + 0.5 sum_f (S_r[f]^2 - Q_r[f])
@@ -21,7 +28,8 @@ With dz_r = (sigmoid(z_r) - y_r) / B:
 The tables take FMTrainer's row-local rule, the tower `dense_optimizer` (a fused optimizer of
 optim/), b the dense form of the tables' rule as in FMTrainer.
 
-One GPU: the step is dfm_rows (csrc/kernels/deepfm.hip: bags, tower, head and the backward through
+One GPU: the step is dfm_rows (csrc/kernels/deepfm.hip; with fields dfmf_rows,
+csrc/kernels/deepfm_fields.hip: bags, tower, head and the backward through
 the tower in one launch), a gemm and a col_sum per layer for the weight gradients, the fixed-order
 sums, fm.hip's one-writer table update and the two dense optimizer launches; evaluation is dfm_rows
 plus the evaluation record's reduce.  On the CPU, or with DTF_DFM_FUSED=0, a short torch fp32 path
@@ -41,15 +49,19 @@ from .fm import FMTrainer
 class DeepFMTrainer(FMTrainer):
     def __init__(self, num_features: int, factors: int = 8, hidden: Sequence[int] = (256, 128),
                  dense_optimizer: str = "adam", dense_lr: Optional[float] = None, dense_hp: Optional[dict] = None,
-                 **fm):
+                 num_fields: Optional[int] = None, **fm):
         """fm: FMTrainer's keyword arguments (lr, world, seed, device, init_std, optimizer, optimizer_hp,
-        auc_bins); dense_lr None: lr."""
+        auc_bins); dense_lr None: lr.  num_fields P: the tower reads P concatenated per-field embeddings and the
+        batches are in the bag form (offsets [B * P + 1]); None: the pooled factors, CSR rows."""
         super().__init__(num_features, factors, **fm)
         self.hidden = tuple(int(h) for h in hidden)
         if not self.hidden or min(self.hidden) < 1:
             raise ValueError("DeepFMTrainer: hidden must name at least one positive width")
+        if num_fields is not None and int(num_fields) < 1:
+            raise ValueError("DeepFMTrainer: num_fields must be at least 1 (None: no fields)")
+        self.num_fields = None if num_fields is None else int(num_fields)
         g = torch.Generator().manual_seed(int(fm.get("seed", 1)) + 2)       # the tower as WideDeep initialises its own
-        dims = [self.factors] + list(self.hidden) + [1]
+        dims = [self.factors * (self.num_fields or 1)] + list(self.hidden) + [1]
         self.layers = []
         for i in range(len(dims) - 1):
             w = torch.randn(dims[i], dims[i + 1], generator=g) * (2.0 / dims[i]) ** 0.5
@@ -74,9 +86,10 @@ class DeepFMTrainer(FMTrainer):
             ok = self.device.type == "cuda" and os.environ.get("DTF_DFM_FUSED", "1") != "0"
             if ok:
                 from .. import _native
-                if not _native.load().DeepFMPlan.supported(self.factors, list(self.hidden)):
-                    raise ValueError(f"DeepFMTrainer: the fused step takes factors a multiple of 4 in 4 .. 128 and 1 to "
-                                     f"3 hidden widths, multiples of 16 up to 512, not {self.factors} / {self.hidden} "
+                if not _native.load().DeepFMPlan.supported(self.factors, list(self.hidden), self.num_fields or 0):
+                    raise ValueError(f"DeepFMTrainer: the fused step takes factors a multiple of 4 in 4 .. 128, 1 to "
+                                     f"3 hidden widths, multiples of 16 up to 512, and at most 64 fields with fields * "
+                                     f"factors <= 512, not {self.factors} / {self.hidden} / {self.num_fields} "
                                      f"(DTF_DFM_FUSED=0 runs the torch path)")
             self._fused = ok
         return ok
@@ -86,22 +99,39 @@ class DeepFMTrainer(FMTrainer):
     def _native_plan(self):
         if self._plan is None:
             from .. import _native
-            self._plan = _native.load().DeepFMPlan(self.w, self.V, self.layers, self.b)   # the tensors themselves
+            self._plan = _native.load().DeepFMPlan(self.w, self.V, self.layers, self.b,     # the tensors themselves
+                                                   num_fields=self.num_fields or 0)
         return self._plan
+
+    def _parts(self, batch):
+        labels, offsets, ids, vals = super()._parts(batch)
+        if self.num_fields is not None and offsets.numel() != labels.numel() * self.num_fields + 1:
+            raise ValueError("DeepFMTrainer: with num_fields, offsets must hold B * num_fields + 1 entries, one bag per "
+                             "(row, field); ffm_batch makes them from a field per entry")
+        return labels, offsets, ids, vals
 
     # ----------------------------------------------------------------- the torch path
     def _forward_general(self, offsets, ids, vals):
-        """FMTrainer's tuple with the tower's score added to z, and the activations [a_0 = S, ..., a_nh] after it."""
-        z, S, row, idk, x = super()._forward_general(offsets, ids, vals)
-        acts = [S]
+        """FMTrainer's tuple with the tower's score added to z, then the activations [a_0, ..., a_nh] and the bag of
+        each kept entry: a_0 = S and the entry's row, or with fields the [B, P * K] concatenation and bag r * P + p."""
+        P = self.num_fields
+        z, S, row, idk, x = super()._forward_general(offsets if P is None else offsets[::P], ids, vals)
+        a0, bag = S, row
+        if P is not None:
+            nb = offsets.numel() - 1
+            bag = torch.repeat_interleave(torch.arange(nb, device=ids.device), torch.diff(offsets))
+            bag = bag[(ids >= 0) & (ids < self.num_features)]
+            a0 = torch.zeros(nb, self.factors, dtype=torch.float32, device=ids.device)
+            a0 = a0.index_add_(0, bag, self.V[idk] * x[:, None]).view(nb // P, P * self.factors)
+        acts = [a0]
         for l in range(len(self.hidden)):
             acts.append(torch.relu(acts[-1] @ self.layers[2 * l] + self.layers[2 * l + 1]))
         t = acts[-1] @ self.layers[-2] + self.layers[-1]
-        return z + t.reshape(-1), S, row, idk, x, acts
+        return z + t.reshape(-1), S, row, idk, x, acts, bag
 
     @torch.no_grad()
     def _train_step_general(self, labels, offsets, ids, vals) -> torch.Tensor:
-        z, S, row, idk, x, acts = self._forward_general(offsets, ids, vals)
+        z, S, row, idk, x, acts, bag = self._forward_general(offsets, ids, vals)
         loss = ops.sigmoid_xent(z, labels)
         dz = (torch.sigmoid(z) - labels) / labels.numel()
         # the tower's backward: the gradient at each pre-activation, the weight gradients, da_0
@@ -113,13 +143,16 @@ class DeepFMTrainer(FMTrainer):
             g = g @ self.layers[2 * l].t()
             if l > 0:
                 g = g * (acts[l] > 0)
-        demb = dz[:, None] * S + g
+        if self.num_fields is None:
+            demb = dz[:, None] * S + g
+        else:                                                       # [B * P, K]: dz S on every block of da_0
+            demb = ((dz[:, None] * S)[:, None, :] + g.view(-1, self.num_fields, self.factors)).reshape(-1, self.factors)
         touched, inv = torch.unique(idk, return_inverse=True)
         xdz = x * dz[row]
         gw = torch.zeros(touched.numel(), dtype=torch.float32, device=z.device).index_add_(0, inv, xdz)
         q = torch.zeros_like(gw).index_add_(0, inv, x * xdz)
         gV = torch.zeros(touched.numel(), self.factors, dtype=torch.float32, device=z.device)
-        gV.index_add_(0, inv, x[:, None] * demb[row])
+        gV.index_add_(0, inv, x[:, None] * demb[bag])
         gV -= self.V[touched] * q[:, None]
         for table, slots, gt in ((self.w, self.w_slots, gw), (self.V, self.V_slots, gV)):
             rows = [table[touched]] + [s[touched] for s in slots.values()]
@@ -133,7 +166,7 @@ class DeepFMTrainer(FMTrainer):
     # ----------------------------------------------------------------- the fused step
     @torch.no_grad()
     def _train_step_fused(self, labels, offsets, ids, vals) -> torch.Tensor:
-        """dfm_rows, the weight gradients (beta = 0) by the general path's gemm / col_sum launches, the fixed-order
+        """dfm_rows (with fields: dfmf_rows), the weight gradients (beta = 0) by the general path's gemm / col_sum launches, the fixed-order
         sums, the one-writer table update and the dense rules: no router, dedup or autograd.  The returned loss
         is a copy: the plan's own is overwritten by the next step."""
         from .. import _native

@@ -1,6 +1,7 @@
 """Cost of a factorization-machine training step and evaluation on one GPU, through FMTrainer's public interface:
 
     python scripts/bench_fm.py [--features 100000000] [--rounds 3] [--out FILE] [--hidden 512,256] [--fields 22]
+                               [--tower-fields 39]
 
 F = 1e8 features, K = 64 factors, about 40 ids per row (Zipf-hot), SGD, device-resident batches of 500 and 4096
 rows.  Two variants, measured in alternating fresh child processes, `--rounds` each: the fused path
@@ -22,6 +23,11 @@ fused FM step next to both; no rows-per-wave sweep.  The record then also lists 
 csrc/kernels/ffm.hip): one entry per field and row (Zipf-hot ids), the batch in the (row, field) bag form; its fused
 path against its torch path (DTF_FFM_FUSED=0, the baseline: there was no FFM before); no rows-per-wave sweep, and the
 record lists every run.
+
+--tower-fields P (with --hidden): DeepFM with fields (DeepFMTrainer(num_fields=P) with K = 8 factors,
+csrc/kernels/deepfm_fields.hip): one entry per field and row, the batch in the bag form; its fused path against its
+torch path (DTF_DFM_FUSED=0, the baseline: there was no field form before) and, for context, the pooled DeepFM at
+K = 64 of the same build and tower (its own batches of about 40 ids per row).  The record lists every run.
 
 What a step must move at B = 4096: 4096 x 40 table rows x 256 B = 42 MB of random 256-byte reads in fm_rows, and
 per distinct id one 256-byte read and write in the update.
@@ -71,7 +77,7 @@ def _stream_ms(torch, fn, reps=20, warmup=5, inner=10):
     return float(np.median(out))
 
 
-def worker(tree, F, hidden=(), fields=0):
+def worker(tree, F, hidden=(), fields=0, tower_fields=0):
     sys.path.insert(0, tree)
     import torch
 
@@ -83,6 +89,9 @@ def worker(tree, F, hidden=(), fields=0):
     rng = np.random.default_rng(0)
     if fields:
         m = FFMTrainer(F, num_fields=fields, factors=4, lr=0.05, world=World(device=dev))
+    elif tower_fields:
+        m = DeepFMTrainer(F, factors=8, hidden=hidden, num_fields=tower_fields, lr=0.05, world=World(device=dev))
+        fields = tower_fields                      # the batches: one entry per (row, field) bag
     elif hidden:
         m = DeepFMTrainer(F, factors=64, hidden=hidden, lr=0.05, world=World(device=dev))
     else:
@@ -95,7 +104,7 @@ def worker(tree, F, hidden=(), fields=0):
         res[f"evaluate_{B}_event_ms"] = _stream_ms(torch, lambda b=b: m.evaluate(b))
     if res["fused"]:
         plan = m._native_plan()
-        for B, b in ({} if hidden or fields else batches).items():
+        for B, b in ({} if hidden or fields else batches).items():     # (the plain FM only)
             res[f"rpw_auto_{B}"] = int(plan.rpw_for(B))
             for r in RPWS:
                 plan.set_rpw(r)
@@ -117,9 +126,13 @@ def main():
     ap.add_argument("--worker", default="")
     ap.add_argument("--hidden", default="", help="DeepFM's hidden widths, e.g. 512,256 (default: the plain FM)")
     ap.add_argument("--fields", type=int, default=0, help="the field-aware FM with this many fields of 4 factors")
+    ap.add_argument("--tower-fields", type=int, default=0,
+                    help="with --hidden: DeepFM whose tower reads this many concatenated fields of 8 factors")
     a = ap.parse_args()
+    if a.tower_fields and (not a.hidden or a.fields):
+        raise SystemExit("--tower-fields goes with --hidden and without --fields")
     if a.worker:
-        return worker(a.worker, a.features, tuple(int(h) for h in a.hidden.split(",") if h), a.fields)
+        return worker(a.worker, a.features, tuple(int(h) for h in a.hidden.split(",") if h), a.fields, a.tower_fields)
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     variants = [("fused", {"DTF_FM_FUSED": "1"}, ""), ("general_path", {"DTF_FM_FUSED": "0"}, "")]
     if a.hidden:
@@ -127,13 +140,18 @@ def main():
                     ("fm_fused", {"DTF_FM_FUSED": "1"}, "")]
     if a.fields:
         variants = [("fused", {"DTF_FFM_FUSED": "1"}, ""), ("general_path", {"DTF_FFM_FUSED": "0"}, "")]
-    runs = {name: [] for name, _, _ in variants}
+    variants = [v + (0,) for v in variants]
+    if a.tower_fields:
+        variants = [("fused", {"DTF_DFM_FUSED": "1"}, a.hidden, a.tower_fields),
+                    ("general_path", {"DTF_DFM_FUSED": "0"}, a.hidden, a.tower_fields),
+                    ("pooled_fused", {"DTF_DFM_FUSED": "1"}, a.hidden, 0)]
+    runs = {name: [] for name, _, _, _ in variants}
     for r in range(a.rounds):
         # alternating: one process per variant per round, the order reversed every other round
-        for name, env, hidden in (variants if r % 2 == 0 else variants[::-1]):
+        for name, env, hidden, tf in (variants if r % 2 == 0 else variants[::-1]):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", here, "--features",
-                                str(a.features), "--hidden", hidden, "--fields", str(a.fields)], capture_output=True,
-                               text=True, env=dict(os.environ, **env), timeout=300)
+                                str(a.features), "--hidden", hidden, "--fields", str(a.fields), "--tower-fields", str(tf)],
+                               capture_output=True, text=True, env=dict(os.environ, **env), timeout=300)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
             if p.returncode != 0 or not line:
                 raise SystemExit(f"{name} round {r} failed:\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}")
@@ -157,6 +175,11 @@ def main():
     out["fused_faster_beyond_spread"] = {k: bool(f[k]["max"] < g[k]["min"]) for k in g if k.endswith("_ms")}
     if a.fields:
         out.update(fields=a.fields, factors=4, ids_per_row=a.fields, table_row_bytes_read_by_fm_rows_at_4096=4096 * a.fields ** 2 * 16)
+        out["runs"] = {name: {k: [x[k] for x in rs] for k in rs[0] if k.endswith("_ms")} for name, rs in runs.items()}
+    elif a.tower_fields:
+        out.update(hidden=[int(h) for h in a.hidden.split(",")], tower_fields=a.tower_fields, factors=8,
+                   ids_per_row=a.tower_fields, pooled_factors=64, pooled_ids_per_row=40,
+                   table_row_bytes_read_by_fm_rows_at_4096=4096 * a.tower_fields * 32)
         out["runs"] = {name: {k: [x[k] for x in rs] for k in rs[0] if k.endswith("_ms")} for name, rs in runs.items()}
     elif a.hidden:
         out["hidden"] = [int(h) for h in a.hidden.split(",")]
